@@ -2,6 +2,7 @@
 """Headline benchmark: device-resident parse + Toeplitz + LPM classify (Mpps).
 
 python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5]
+                [--dump-outputs DIR] [--full]
 
 One step = one classify pass over one batch resident in HBM (default config
 C3, the l3fwd-graph workload: 16M x 64-B IPv4/UDP frames per GPU, 1024-prefix
@@ -11,7 +12,13 @@ collective); after the K timed steps the per-bin counters are all-reduced
 once over RCCL (the "final per-output-port count reduce").  Rank 0 prints one
 JSON line.  Inputs are generated in HBM (synthetic, seeded) before timing.
 
-The same line carries, besides the headline:
+A plain run does only that: set up, warm up, time the K steps, write the last
+step's outputs (--dump-outputs DIR: what a caller of the timed path receives,
+as DIR/<name>.npy, identical inputs from run to run) and print the line.
+
+With --full the same line carries, besides the headline, the parity checks of
+the batch against the oracle, the same-box probe ceiling and the CPU baseline
+of the headline config, and:
   configs        every other BASELINE config measured the same way (C2, C4,
                  C5), each with its roofline object and its CPU baseline;
   node_boundary  the graph-node boundary over pktmbuf_t bursts of 256 (the
@@ -268,6 +275,44 @@ def run_step(st, stream=None, k: int = 0):
         cl.classify_rewrite(fr, out=out, burst=256, tx_edge=st["tx"], stream=sid)
     else:
         cl.classify(fr, mode, out=out, stream=sid)
+
+
+DUMP_SAMPLE = 1 << 20  # per-packet outputs dumped: at most this many packets (3 x 8 MiB as float64)
+
+
+def dump_outputs(path: str, st, slot: int) -> None:
+    """--dump-outputs: what the last timed step (ring batch `slot`) handed its
+    caller -- the per-packet outputs of the config (OUTPUTS; for c3rw also the
+    tx edges and, of every 8th dumped packet, the first 28 B of the frame
+    rewritten in place, as float32) and the bin counters summed over the timed
+    steps -- as <path>/<name>.npy in float64, which holds every u32 value and
+    every count exactly; under 64 MB in all.  Batches over DUMP_SAMPLE
+    packets are sampled at fixed seeded indices (sorted, with repeats), the
+    same for every run of the same size."""
+    fr, out = st["ring"][slot]
+    n = fr.n
+    os.makedirs(path, exist_ok=True)
+    idx = None
+    if n > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(20).integers(0, n, size=DUMP_SAMPLE))
+        idx = torch.from_numpy(pick).to(fr.slab.device)
+    arrays = {}
+    for key, dt in (("nh", np.uint32), ("hash", np.uint32), ("queue", np.uint16), ("edge", np.uint8)):
+        t = out.get(key)
+        if t is not None:
+            t = t[:n] if idx is None else t[:n].index_select(0, idx)
+            arrays[key] = t.cpu().numpy().view(dt)
+    if "tx" in st:
+        t = st["tx"] if idx is None else st["tx"].index_select(0, idx)
+        arrays["tx_edge"] = t.cpu().numpy()
+        head = fr.slab[: n * fr.stride].view(n, fr.stride)[:, fr.data_off:fr.data_off + 28]
+        rows = torch.arange(0, n, 8, device=fr.slab.device) if idx is None else idx[::8]
+        arrays["frame_head"] = head.index_select(0, rows).cpu().numpy()
+    arrays["bins"] = out["bins"].cpu().numpy().view(np.uint64)
+    for key, a in arrays.items():
+        np.save(os.path.join(path, key + ".npy"), a.astype(np.float32 if key == "frame_head" else np.float64))
+    log(f"[bench] outputs of ring batch {slot} ({'all' if idx is None else DUMP_SAMPLE} of {n} packets) "
+        f"in {path}: {', '.join(sorted(arrays))}")
 
 
 def parity_sample(state, k: int = 1 << 16) -> bool:
@@ -1661,6 +1706,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--packets", type=int, default=0, help="override packets per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: parity against the oracle, the same-box "
+                         "probes, the CPU baselines, the other configs (--extra), the node-boundary, "
+                         "host-memory and route-update rates (each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (and the bin counters of the "
+                         "timed steps) as DIR/<name>.npy (float64); of a batch over 2^20 packets a fixed "
+                         "seeded sample")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -1699,8 +1752,10 @@ def main():
     if args.frame_mem != "default":
         for k in FRAME_MEM:
             FRAME_MEM[k] = None if args.frame_mem == "torch" else args.frame_mem
-    if args.no_imix:
+    if args.no_imix or not args.full:
         args.extra = ""
+    if not args.full:  # a plain run: the headline figure alone
+        args.no_cpu_baseline = args.no_parity = args.no_e2e = args.no_node = args.no_probe = True
 
     from cndp_amd import dist as D
     world, rank, local = setup_dist()
@@ -1759,6 +1814,8 @@ def main():
     kern_ms = ev0.elapsed_time(ev1) / args.steps
 
     elapsed, kern_ms = D.max_over_ranks([elapsed, kern_ms], dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, st, (args.steps - 1) % len(st["ring"]))
     probe = None
     if rank == 0 and not args.no_probe and args.config != "c3rw":
         try:

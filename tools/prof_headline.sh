@@ -10,7 +10,7 @@ tag=${1:-r03}
 out=gpurun_out/headline_$tag
 mkdir -p $out
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run \
-    -- python3 bench.py --steps 100 --no-cpu-baseline --no-e2e --no-node --extra "" \
+    -- python3 bench.py --full --steps 100 --no-cpu-baseline --no-e2e --no-node --extra "" \
     > $out/bench.json 2> $out/bench.log || { echo "profiled bench failed rc=$?"; exit 1; }
 find $out/prof -name '*kernel_trace.csv' -size +20M -delete
 echo done
