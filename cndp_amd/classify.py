@@ -276,6 +276,34 @@ class Classifier:
                                                order.data_ptr(), stream or None), "cndp_gpu_bin_partition")
         return start, order[:n]
 
+    def udp_input(self, frames, out: dict, table, sel=None, n_bins: int | None = None,
+                  stream: int | None = None, l4: dict | None = None) -> dict:
+        """ip4_proto + udp_input (cndp_gpu_udp_input, include/cndp_l4.h) over the
+        frames a cnet classify of `frames` sent to ip4_input's proto edge: `out`
+        is that classify's output dict (nh, rxmeta and, unless `sel` is given,
+        ptype), `table` a PcbTable.  Returns the stage's outputs as tensors
+        (l4edge, pcb, ports, payload_off, bin_of, stats; stats accumulates when
+        a previous result is passed back as `l4`)."""
+        import torch
+        from .l4 import alloc_l4_outputs
+        dev = frames.slab.device
+        if n_bins is None:
+            n_bins = max(1, table.count())
+        if l4 is None:
+            l4 = alloc_l4_outputs(frames.n, dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        b = self.batch(frames, N.CNDP_MODE_CNET, out)
+        io = N.L4Io()
+        io.sel = self._ptr(sel)
+        io.l4edge, io.pcb, io.ports = self._ptr(l4.get("l4edge")), self._ptr(l4.get("pcb")), self._ptr(l4.get("ports"))
+        io.payload_off, io.bin_of = self._ptr(l4.get("payload_off")), self._ptr(l4.get("bin_of"))
+        io.n_bins, io.stats = n_bins, self._ptr(l4.get("stats"))
+        N.check(self._L.cndp_gpu_udp_input(self.h, table.h, ctypes.byref(b), ctypes.byref(io), stream or None),
+                "cndp_gpu_udp_input")
+        l4["n_bins"] = n_bins
+        return l4
+
     def bin_ids(self, mode: int, out: dict, n: int, n_bins: int, stream: int | None = None):
         import torch
         dev = out["queue"].device

@@ -1,0 +1,109 @@
+"""UDP socket demux (include/cndp_l4.h): the PCB table udp_input looks
+frames up in, and the output arrays of Classifier.udp_input.
+
+    tbl = PcbTable(512)
+    i = tbl.add(laddr="10.4.0.7", lport=5000, cksum=True)    # a bound listener
+    out = c.classify(frames, CNDP_MODE_CNET, out=c.alloc_outputs(n, meta=True))
+    l4 = c.udp_input(frames, out, tbl)                       # l4edge, pcb, bin_of, ...
+    start, order = c.bin_partition(l4["bin_of"], l4["n_bins"])   # per-socket receive lists
+
+Addresses and ports are kept in network order, as the u32 / u16 a
+little-endian host loads from the frame; add() and lookup keys take host
+integers or dotted quads and convert.
+"""
+from __future__ import annotations
+
+import ctypes
+import socket
+import struct
+
+import numpy as np
+
+from . import native as N
+
+# struct cndp_pcb_key
+KEY_DT = np.dtype([("laddr", "<u4"), ("faddr", "<u4"), ("lport", "<u2"), ("fport", "<u2")])
+
+
+def addr_net(a) -> int:
+    """An IPv4 address (dotted quad, or a host-order integer such as
+    0x0A000001) as the u32 a little-endian load of its wire bytes gives."""
+    if isinstance(a, str):
+        return struct.unpack("<I", socket.inet_aton(a))[0]
+    return struct.unpack("<I", struct.pack(">I", int(a) & 0xFFFFFFFF))[0]
+
+
+def port_net(p: int) -> int:
+    """A port number as the u16 a little-endian load of its wire bytes gives."""
+    return struct.unpack("<H", struct.pack(">H", int(p) & 0xFFFF))[0]
+
+
+def make_keys(laddr, lport, faddr, fport) -> np.ndarray:
+    """Lookup keys from arrays already in network order."""
+    k = np.zeros(len(np.atleast_1d(lport)), KEY_DT)
+    k["laddr"], k["lport"], k["faddr"], k["fport"] = laddr, lport, faddr, fport
+    return k
+
+
+class PcbTable:
+    """cndp_pcb_* (include/cndp_l4.h): the stack's UDP PCB vector."""
+
+    def __init__(self, max_entries: int = 512):
+        self._L = N.lib()
+        h = ctypes.c_void_p()
+        N.check(self._L.cndp_pcb_create(max_entries, ctypes.byref(h)), "cndp_pcb_create")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self._L.cndp_pcb_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_raw(self, laddr: int, faddr: int, lport: int, fport: int, opt_flag: int = 0) -> int:
+        """cndp_pcb_add on network-order values; returns its result (index or -errno)."""
+        e = N.PcbEntry(laddr, faddr, lport, fport, opt_flag)
+        return self._L.cndp_pcb_add(self.h, ctypes.byref(e))
+
+    def add(self, laddr=0, lport: int = 0, faddr=0, fport: int = 0, cksum: bool = False) -> int:
+        """A socket bound to laddr:lport (0 = any), optionally connected to
+        faddr:fport; cksum sets UDP_CHKSUM_FLAG.  Returns the PCB index."""
+        return N.check(self.add_raw(addr_net(laddr), addr_net(faddr), port_net(lport), port_net(fport),
+                                    N.CNDP_UDP_CHKSUM_FLAG if cksum else 0), "cndp_pcb_add")
+
+    def delete(self, idx: int) -> int:
+        """cndp_pcb_del; returns its result (0 or -errno)."""
+        return self._L.cndp_pcb_del(self.h, idx)
+
+    def set_flags(self, punt_enabled: bool = True, tcp_enabled: bool = False) -> None:
+        N.check(self._L.cndp_pcb_set_flags(self.h, int(punt_enabled), int(tcp_enabled)), "cndp_pcb_set_flags")
+
+    def count(self) -> int:
+        return N.check(self._L.cndp_pcb_count(self.h), "cndp_pcb_count")
+
+    def lookup(self, keys: np.ndarray) -> np.ndarray:
+        """cndp_pcb_lookup over a KEY_DT array (make_keys): u32 indices,
+        CNDP_PCB_NONE for no match."""
+        keys = np.ascontiguousarray(keys, dtype=KEY_DT)
+        out = np.empty(len(keys), np.uint32)
+        N.check(self._L.cndp_pcb_lookup(self.h, keys.ctypes.data, len(keys), out.ctypes.data),
+                "cndp_pcb_lookup")
+        return out
+
+
+def alloc_l4_outputs(n: int, device) -> dict:
+    """The output arrays of cndp_gpu_udp_input as torch tensors (signed
+    dtypes of the same width, as Classifier.alloc_outputs uses)."""
+    import torch
+    m = max(n, 1)
+    return {"l4edge": torch.empty(m, dtype=torch.uint8, device=device)[:n],
+            "pcb": torch.empty(m, dtype=torch.int32, device=device)[:n],
+            "ports": torch.empty(m, dtype=torch.int32, device=device)[:n],
+            "payload_off": torch.empty(m, dtype=torch.int16, device=device)[:n],
+            "bin_of": torch.empty(m, dtype=torch.int16, device=device)[:n],
+            "stats": torch.zeros(4, dtype=torch.int64, device=device)}

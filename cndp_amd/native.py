@@ -1,5 +1,5 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
-include/cndp_node.h and include/cndp_gpu.h).
+include/cndp_node.h, include/cndp_gpu.h and include/cndp_l4.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -65,6 +65,21 @@ CNDP_MBUF_EDGE_CLS_DROP = 0xFFFF
 IP4_LOOKUP_NEXT_REWRITE, IP4_LOOKUP_NEXT_PKT_DROP = 0, 1
 IP4_INPUT_NEXT_PKT_DROP, IP4_INPUT_NEXT_FORWARD, IP4_INPUT_NEXT_PROTO = 0, 1, 2
 
+# cndp_l4.h
+CNDP_PCB_MAX_ENTRIES = 4096
+CNDP_PCB_NONE = 0xFFFFFFFF
+CNDP_UDP_CHKSUM_FLAG = 0x0080
+CNDP_L4_NODE_IP4_PROTO, CNDP_L4_NODE_UDP_INPUT = 0, 1
+CNDP_L4_EDGE_NONE = 0xFF
+CNDP_IP4_PROTO_DROP, CNDP_IP4_PROTO_TCP = 0, 2
+CNDP_UDP_INPUT_PKT_DROP, CNDP_UDP_INPUT_CHNL_RECV, CNDP_UDP_INPUT_PKT_PUNT = 0, 1, 2
+CNDP_L4_STAT_RECV, CNDP_L4_STAT_NOMATCH, CNDP_L4_STAT_CKSUM, CNDP_L4_STAT_PROTO_DROP = 0, 1, 2, 3
+
+
+def CNDP_L4_EDGE(node: int, e: int) -> int:
+    return (node << 4) | e
+
+
 MS_RSS_KEY = bytes.fromhex(
     "6d5a56da255b0ec24167253d43a38fb0d0ca2bcbae7b30b477cb2da38030f20c6a42b73bbeac01fa")
 
@@ -102,6 +117,19 @@ class MqConf(Structure):
     _fields_ = [("mode", c_uint32), ("flags", c_uint32), ("batch", c_uint32), ("depth", c_uint32),
                 ("max_delay_us", c_uint32), ("stage_max", c_uint32), ("umem", c_void_p),
                 ("lport", c_uint16), ("rsvd", c_uint16 * 3), ("metadata", c_void_p)]
+
+
+class PcbEntry(Structure):
+    """struct cndp_pcb_entry (cndp_l4.h)."""
+    _fields_ = [("laddr", c_uint32), ("faddr", c_uint32), ("lport", c_uint16), ("fport", c_uint16),
+                ("opt_flag", c_uint16)]
+
+
+class L4Io(Structure):
+    """struct cndp_l4_io (cndp_l4.h)."""
+    _fields_ = [("sel", c_void_p), ("l4edge", c_void_p), ("pcb", c_void_p), ("ports", c_void_p),
+                ("payload_off", c_void_p), ("bin_of", c_void_p), ("n_bins", c_uint32),
+                ("stats", c_void_p)]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -198,6 +226,15 @@ def lib():
         "cndp_gpu_mq_stat": (ctypes.c_int64, [c_void_p, c_int]),
         "cndp_gpu_get_stat": (ctypes.c_int64, [c_void_p, c_int]),
         "cndp_gpu_version": (c_char_p, []),
+        # cndp_l4.h
+        "cndp_pcb_create": (c_int, [c_uint32, POINTER(c_void_p)]),
+        "cndp_pcb_free": (None, [c_void_p]),
+        "cndp_pcb_add": (c_int, [c_void_p, POINTER(PcbEntry)]),
+        "cndp_pcb_del": (c_int, [c_void_p, c_uint32]),
+        "cndp_pcb_set_flags": (c_int, [c_void_p, c_int, c_int]),
+        "cndp_pcb_count": (c_int, [c_void_p]),
+        "cndp_pcb_lookup": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+        "cndp_gpu_udp_input": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(L4Io), c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -217,6 +254,14 @@ def exported_symbols():
             txt = f.read()
         names += re.findall(r"^[A-Za-z_][\w \*]*?\b((?:cne|cndp|ip4)_\w+)\s*\(", txt, re.M)
     return sorted(set(n for n in names if not n.endswith("_fn_t")))
+
+
+def l4_exported_symbols():
+    """Names include/cndp_l4.h declares."""
+    import re
+    with open(os.path.join(os.path.dirname(HERE), "include", "cndp_l4.h")) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"^[A-Za-z_][\w \*]*?\b(cndp_\w+)\s*\(", txt, re.M)))
 
 
 def check(rc: int, what: str) -> int:

@@ -417,3 +417,83 @@ def cndpfwd_udp(n: int, pkt_len: int = 60, src_mac: bytes = bytes.fromhex("02000
     f[34:34 + len(udp)] = udp[: 64 - 34]
     slab = torch.tensor(list(bytes(f)) * n, dtype=torch.uint8)
     return Frames(slab, n, stride=64, lengths=torch.full((n,), pkt_len, dtype=torch.int64))
+
+
+def udp_socket_frames(n: int, sockets, foreign=((0xC6120001, 9),), seed: int = 1,
+                      payload_lens=(0, 1, 18, 64), ihl=(5,), vlan_frac: float = 0.0,
+                      cksum=("ok",), layout: str = "packed", slot: int = 128, align: int = 1,
+                      proto=(17,), device="cpu") -> Frames:
+    """Frames addressed to local UDP sockets (the traffic udp_input terminates).
+
+    sockets / foreign: [(IPv4 address as a host-order integer, port)]; frame i
+    goes from a drawn foreign pair to a drawn socket.  Per frame, drawn from
+    the given tuples with a seeded generator: the UDP payload length, the IPv4
+    IHL (5..15, options are NOPs), the protocol byte, and how the UDP checksum
+    is set -- "ok" (cne_ipv4_udptcp_cksum's value, 0 sent as 0xffff), "bad"
+    (that value + 1) or "zero" (no checksum).  vlan_frac of the frames carry
+    one 802.1Q tag.  The IPv4 header checksum is always valid.
+    layout: "packed" (fixed `slot`-byte slots; a frame longer than the slot is
+    cut), "umem" (2 KiB frames, data at +256) or "offsets" (frames laid end to
+    end, each start rounded up to `align`: 1 puts frames at odd addresses).
+    Frames.lengths holds the frame bytes."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    pick = lambda seq: [seq[k] for k in rng.integers(0, len(seq), n)]  # noqa: E731
+    socks, fors = pick(list(sockets)), pick(list(foreign))
+    pls, ihls, cks, protos = pick(list(payload_lens)), pick(list(ihl)), pick(list(cksum)), pick(list(proto))
+    tagged = rng.random(n) < vlan_frac
+    frames = []
+    for i in range(n):
+        hl, pl = ihls[i] * 4, pls[i]
+        (dst, dport), (src, sport) = socks[i], fors[i]
+        tot = hl + 8 + pl
+        ip = bytearray(hl)
+        ip[0] = 0x40 | ihls[i]
+        ip[2:4] = tot.to_bytes(2, "big")
+        ip[4:6] = int(rng.integers(0, 65536)).to_bytes(2, "big")
+        ip[8], ip[9] = 64, protos[i]
+        ip[12:16], ip[16:20] = src.to_bytes(4, "big"), dst.to_bytes(4, "big")
+        for k in range(20, hl):
+            ip[k] = 1
+        s = sum(int.from_bytes(ip[k:k + 2], "big") for k in range(0, hl, 2))
+        s = (s >> 16) + (s & 0xFFFF)
+        s = (s >> 16) + (s & 0xFFFF)
+        ip[10:12] = ((~s) & 0xFFFF).to_bytes(2, "big")
+        udp = bytearray(sport.to_bytes(2, "big") + dport.to_bytes(2, "big") + (8 + pl).to_bytes(2, "big")
+                        + b"\0\0" + rng.integers(0, 256, pl, dtype=np.uint8).tobytes())
+        if cks[i] != "zero":
+            data = bytes(ip[12:20]) + bytes([0, protos[i]]) + (8 + pl).to_bytes(2, "big") + bytes(udp)
+            data += b"\0" * (len(data) & 1)
+            c = sum(int.from_bytes(data[k:k + 2], "big") for k in range(0, len(data), 2))
+            while c >> 16:
+                c = (c >> 16) + (c & 0xFFFF)
+            c = ((~c) & 0xFFFF) or 0xFFFF
+            if cks[i] == "bad":
+                c = (c + 1) & 0xFFFF or 1
+            udp[6:8] = c.to_bytes(2, "big")
+        eth = bytes.fromhex("020000000001020000000002") + (b"\x81\x00\x00\x05" if tagged[i] else b"") + b"\x08\x00"
+        frames.append(eth + bytes(ip) + bytes(udp))
+    lens = np.array([len(f) for f in frames], np.int64)
+    data_off = 0
+    if layout == "packed":
+        stride, offs = slot, np.arange(n, dtype=np.int64) * slot
+        total = n * slot
+    elif layout == "umem":
+        stride, data_off, offs = 2048, 256, np.arange(n, dtype=np.int64) * 2048
+        total = n * 2048
+    else:
+        stride, offs, at = 0, np.zeros(n, np.int64), 0
+        for i in range(n):
+            at = (at + align - 1) // align * align
+            offs[i] = at
+            at += int(lens[i])
+        total = at
+    buf = np.zeros(max(total, 1), np.uint8)
+    for i, f in enumerate(frames):
+        room = slot if layout == "packed" else (2048 - 256 if layout == "umem" else len(f))
+        f = f[:room]
+        o = int(offs[i]) + data_off
+        buf[o:o + len(f)] = np.frombuffer(f, np.uint8)
+    slab = torch.from_numpy(buf).to(device)
+    return Frames(slab, n, stride=stride, data_off=data_off, lengths=torch.from_numpy(lens),
+                  offsets=torch.from_numpy(offs).to(device) if layout == "offsets" else None)
