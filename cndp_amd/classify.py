@@ -304,6 +304,38 @@ class Classifier:
         l4["n_bins"] = n_bins
         return l4
 
+    def tcp_input(self, frames, out: dict, table, l4: dict | None = None, sel=None,
+                  n_bins: int | None = None, stream: int | None = None, tcp: dict | None = None) -> dict:
+        """tcp_input's lookup, checksum and segment record (cndp_gpu_tcp_input,
+        include/cndp_tcp.h).  `out` is the cnet classify's output dict (rxmeta),
+        `table` the PcbTable holding the TCP vector.  Without `sel` the frames
+        taken are the ones udp_input's result `l4` has on ip4_proto's tcp edge,
+        and l4["l4edge"] is updated in place; with `sel` (a uint8 tensor) it
+        alone decides and `l4` may be None.  Returns the stage's outputs as
+        tensors (l4edge, pcb, ports, seg, bin_of, stats; stats accumulates when
+        a previous result is passed back as `tcp`)."""
+        import torch
+        from .l4 import alloc_tcp_outputs
+        dev = frames.slab.device
+        if sel is None and l4 is None and tcp is None:
+            raise ValueError("tcp_input needs udp_input's result (l4=) or a selection (sel=)")
+        if n_bins is None:
+            n_bins = max(1, table.count())
+        if tcp is None:
+            tcp = alloc_tcp_outputs(frames.n, dev, l4edge=None if l4 is None else l4["l4edge"])
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        b = self.batch(frames, N.CNDP_MODE_CNET, out)
+        io = N.TcpIo()
+        io.sel = self._ptr(sel)
+        io.l4edge, io.pcb, io.ports = self._ptr(tcp.get("l4edge")), self._ptr(tcp.get("pcb")), self._ptr(tcp.get("ports"))
+        io.seg, io.bin_of = self._ptr(tcp.get("seg")), self._ptr(tcp.get("bin_of"))
+        io.n_bins, io.stats = n_bins, self._ptr(tcp.get("stats"))
+        N.check(self._L.cndp_gpu_tcp_input(self.h, table.h, ctypes.byref(b), ctypes.byref(io), stream or None),
+                "cndp_gpu_tcp_input")
+        tcp["n_bins"] = n_bins
+        return tcp
+
     def bin_ids(self, mode: int, out: dict, n: int, n_bins: int, stream: int | None = None):
         import torch
         dev = out["queue"].device

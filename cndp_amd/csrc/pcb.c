@@ -2,8 +2,10 @@
  * pcb.c -- the UDP PCB table of include/cndp_l4.h: what udp_input reads of the
  * stack's PCB vector (struct pcb_hd, lib/cnet/pcb/cnet_pcb.h:57-60), its
  * best-match lookup on the host (pcb_v4_lookup, cnet_pcb.c:41-92) and the
- * sorted image the device stage mirrors.  Plain C, no HIP: it also builds into
- * a stand-alone program (tests/l4_host).
+ * sorted image the device stage mirrors.  A table that holds the TCP vector
+ * (include/cndp_tcp.h) gets a second image, an exact 4-tuple hash plus per-port
+ * wildcard runs, which also answers cndp_pcb_lookup_indexed.  Plain C, no HIP:
+ * it also builds into stand-alone programs (tests/l4_host, tests/tcp_host).
  */
 #include <errno.h>
 #include <stdlib.h>
@@ -51,10 +53,13 @@ void cndp_pcb_free(cndp_pcb_tbl_t *t)
         return;
     if (t->dev && t->dev_release)
         t->dev_release(t->dev);
+    if (t->tdev && t->tdev_release)
+        t->tdev_release(t->tdev);
     pthread_mutex_destroy(&t->lock);
     free(t->vec);
     free(t->closed);
     free(t->img);
+    free(t->timg);
     free(t);
 }
 
@@ -215,4 +220,89 @@ int pcb_image(struct cndp_pcb_tbl *t)
     t->img_words = words;
     t->img_gen = t->gen;
     return 0;
+}
+
+/* ---- TCP index image (pcb_internal.h) ----------------------------------- */
+static int is_full(const struct cndp_pcb_entry *e) { return e->laddr != 0 && e->faddr != 0; }
+
+int pcb_tcp_image(struct cndp_pcb_tbl *t)
+{
+    if (t->timg_gen == t->gen)
+        return 0;
+    if (!t->timg) { /* sized for the fullest table: both hashes at 2 * max slots */
+        uint32_t hm = pow2_ceil(2u * t->max);
+        t->timg = calloc(TCB_IMG_WORDS((size_t)t->max, hm, hm), sizeof(uint32_t));
+        if (!t->timg)
+            return -ENOMEM;
+    }
+    uint32_t n = t->count;
+    uint32_t *key = malloc((n ? n : 1u) * sizeof(uint32_t));
+    if (!key)
+        return -ENOMEM;
+    uint32_t nfull = 0;
+    for (uint32_t i = 0; i < n; i++) { /* lport << 13 | fully specified << 12 | index */
+        uint32_t f = (uint32_t)is_full(&t->vec[i]);
+        nfull += f;
+        key[i] = (uint32_t)t->vec[i].lport << 13 | f << 12 | i;
+    }
+    qsort(key, n, sizeof(uint32_t), by_port_index);
+    uint32_t ports = 0;
+    for (uint32_t j = 0; j < n; j++)
+        ports += j == 0 || (key[j] >> 13) != (key[j - 1] >> 13);
+    uint32_t HE = pow2_ceil(2u * nfull), HP = pow2_ceil(2u * ports);
+    uint32_t *img = t->timg;
+    uint32_t *laddr = img + TCB_IMG_HDR, *faddr = laddr + n, *pp = faddr + n, *es = pp + n, *ps = es + HE;
+    uint16_t *idx = (uint16_t *)(ps + HP);
+    uint32_t words = TCB_IMG_WORDS(n, HE, HP);
+    memset(img, 0, words * sizeof(uint32_t));
+    img[0] = n;
+    img[1] = HE;
+    img[2] = t->flags;
+    img[3] = words;
+    img[4] = HP;
+    img[5] = nfull;
+    for (uint32_t j = 0; j < n; j++) {
+        uint32_t i = key[j] & 0xfffu;
+        const struct cndp_pcb_entry *e = &t->vec[i];
+        laddr[j] = e->laddr;
+        faddr[j] = e->faddr;
+        pp[j] = (uint32_t)e->fport | (uint32_t)e->lport << 16;
+        idx[j] = (uint16_t)i;
+        if (j == 0 || (key[j] >> 13) != (key[j - 1] >> 13)) {
+            uint32_t h = pcb_port_hash(e->lport, HP);
+            while (ps[h] & PCB_SLOT_VALID)
+                h = (h + 1u) & (HP - 1u);
+            ps[h] = PCB_SLOT_VALID | (uint32_t)e->lport << 12 | j;
+        }
+        if (is_full(e)) { /* positions rise with the index within a port: the first of equal tuples stays */
+            uint32_t x = pcb_tcp_hash(e->laddr, e->faddr, pp[j]), h = x & (HE - 1u);
+            int dup = 0;
+            while (es[h] & PCB_SLOT_VALID) {
+                uint32_t q = es[h] & 0xfffu;
+                if (laddr[q] == e->laddr && faddr[q] == e->faddr && pp[q] == pp[j]) {
+                    dup = 1;
+                    break;
+                }
+                h = (h + 1u) & (HE - 1u);
+            }
+            if (!dup)
+                es[h] = PCB_SLOT_VALID | (x >> 13) << 12 | j;
+        }
+    }
+    free(key);
+    t->timg_words = words;
+    t->timg_gen = t->gen;
+    return 0;
+}
+
+int cndp_pcb_lookup_indexed(cndp_pcb_tbl_t *t, const struct cndp_pcb_key *keys, uint32_t n, uint32_t *idx_out)
+{
+    if (!t || (n && (!keys || !idx_out)))
+        return -EINVAL;
+    pthread_mutex_lock(&t->lock);
+    int r = pcb_tcp_image(t);
+    for (uint32_t k = 0; !r && k < n; k++)
+        idx_out[k] = pcb_tcp_lookup(t->timg, keys[k].laddr, keys[k].faddr, keys[k].lport, keys[k].fport);
+    pthread_mutex_unlock(&t->lock);
+    return r;
 }

@@ -1,11 +1,22 @@
-"""UDP socket demux (include/cndp_l4.h): the PCB table udp_input looks
-frames up in, and the output arrays of Classifier.udp_input.
+"""UDP and TCP socket demux (include/cndp_l4.h, include/cndp_tcp.h): the PCB
+table udp_input / tcp_input look frames up in, and the output arrays of
+Classifier.udp_input and Classifier.tcp_input.
 
     tbl = PcbTable(512)
     i = tbl.add(laddr="10.4.0.7", lport=5000, cksum=True)    # a bound listener
     out = c.classify(frames, CNDP_MODE_CNET, out=c.alloc_outputs(n, meta=True))
     l4 = c.udp_input(frames, out, tbl)                       # l4edge, pcb, bin_of, ...
     start, order = c.bin_partition(l4["bin_of"], l4["n_bins"])   # per-socket receive lists
+
+The TCP vector is a second table; its frames are the ones udp_input left on
+ip4_proto's tcp edge:
+
+    tcp = PcbTable(4096)
+    tcp.add(laddr="10.4.0.7", lport=80)                      # a listener
+    tcp.add(laddr="10.4.0.7", lport=80, faddr="198.18.0.1", fport=40000)   # a connection
+    tbl.set_flags(tcp_enabled=True)
+    l4 = c.udp_input(frames, out, tbl)
+    t = c.tcp_input(frames, out, tcp, l4=l4)                 # l4edge (in place), pcb, seg, bin_of, ...
 
 Addresses and ports are kept in network order, as the u32 / u16 a
 little-endian host loads from the frame; add() and lookup keys take host
@@ -23,6 +34,9 @@ from . import native as N
 
 # struct cndp_pcb_key
 KEY_DT = np.dtype([("laddr", "<u4"), ("faddr", "<u4"), ("lport", "<u2"), ("fport", "<u2")])
+# struct cndp_tcp_seg
+SEG_DT = np.dtype([("seq", "<u4"), ("ack", "<u4"), ("wnd", "<u2"), ("urp", "<u2"), ("len", "<u2"),
+                   ("flags", "u1"), ("offset", "u1")])
 
 
 def addr_net(a) -> int:
@@ -95,6 +109,15 @@ class PcbTable:
                 "cndp_pcb_lookup")
         return out
 
+    def lookup_indexed(self, keys: np.ndarray) -> np.ndarray:
+        """cndp_pcb_lookup_indexed: lookup()'s results, answered from the
+        table's TCP index (exact 4-tuple hash + per-port wildcard runs)."""
+        keys = np.ascontiguousarray(keys, dtype=KEY_DT)
+        out = np.empty(len(keys), np.uint32)
+        N.check(self._L.cndp_pcb_lookup_indexed(self.h, keys.ctypes.data, len(keys), out.ctypes.data),
+                "cndp_pcb_lookup_indexed")
+        return out
+
 
 def alloc_l4_outputs(n: int, device) -> dict:
     """The output arrays of cndp_gpu_udp_input as torch tensors (signed
@@ -107,3 +130,25 @@ def alloc_l4_outputs(n: int, device) -> dict:
             "payload_off": torch.empty(m, dtype=torch.int16, device=device)[:n],
             "bin_of": torch.empty(m, dtype=torch.int16, device=device)[:n],
             "stats": torch.zeros(4, dtype=torch.int64, device=device)}
+
+
+def alloc_tcp_outputs(n: int, device, l4edge=None) -> dict:
+    """The output arrays of cndp_gpu_tcp_input as torch tensors.  seg is an
+    (n, 4) int32 tensor, one 16-byte struct cndp_tcp_seg per row
+    (seg_records() views it as SEG_DT).  l4edge: udp_input's tensor, to be
+    updated in place; otherwise (for a call with `sel`) a fresh one holding
+    CNDP_L4_EDGE_NONE, which is what a frame the stage does not take keeps."""
+    import torch
+    m = max(n, 1)
+    return {"l4edge": l4edge if l4edge is not None else torch.full((m,), N.CNDP_L4_EDGE_NONE, dtype=torch.uint8,
+                                                                    device=device)[:n],
+            "pcb": torch.empty(m, dtype=torch.int32, device=device)[:n],
+            "ports": torch.empty(m, dtype=torch.int32, device=device)[:n],
+            "seg": torch.empty((m, 4), dtype=torch.int32, device=device)[:n],
+            "bin_of": torch.empty(m, dtype=torch.int16, device=device)[:n],
+            "stats": torch.zeros(N.CNDP_TCP_NSTATS, dtype=torch.int64, device=device)}
+
+
+def seg_records(seg) -> np.ndarray:
+    """The seg tensor of Classifier.tcp_input on the host, as SEG_DT records."""
+    return np.ascontiguousarray(seg.cpu().numpy()).view(SEG_DT).reshape(-1)

@@ -1,5 +1,6 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
-include/cndp_node.h, include/cndp_gpu.h and include/cndp_l4.h).
+include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h and
+include/cndp_tcp.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -75,6 +76,13 @@ CNDP_IP4_PROTO_DROP, CNDP_IP4_PROTO_TCP = 0, 2
 CNDP_UDP_INPUT_PKT_DROP, CNDP_UDP_INPUT_CHNL_RECV, CNDP_UDP_INPUT_PKT_PUNT = 0, 1, 2
 CNDP_L4_STAT_RECV, CNDP_L4_STAT_NOMATCH, CNDP_L4_STAT_CKSUM, CNDP_L4_STAT_PROTO_DROP = 0, 1, 2, 3
 
+# cndp_tcp.h
+CNDP_L4_NODE_TCP_INPUT = 2
+CNDP_TCP_INPUT_PKT_DROP, CNDP_TCP_INPUT_SEGMENT, CNDP_TCP_INPUT_PKT_PUNT = 0, 1, 2
+(CNDP_TCP_STAT_SEGMENT, CNDP_TCP_STAT_NOMATCH, CNDP_TCP_STAT_CKSUM, CNDP_TCP_STAT_BADOFF,
+ CNDP_TCP_STAT_RSVD) = range(5)
+CNDP_TCP_NSTATS = 5
+
 
 def CNDP_L4_EDGE(node: int, e: int) -> int:
     return (node << 4) | e
@@ -130,6 +138,12 @@ class L4Io(Structure):
     _fields_ = [("sel", c_void_p), ("l4edge", c_void_p), ("pcb", c_void_p), ("ports", c_void_p),
                 ("payload_off", c_void_p), ("bin_of", c_void_p), ("n_bins", c_uint32),
                 ("stats", c_void_p)]
+
+
+class TcpIo(Structure):
+    """struct cndp_tcp_io (cndp_tcp.h)."""
+    _fields_ = [("sel", c_void_p), ("l4edge", c_void_p), ("pcb", c_void_p), ("ports", c_void_p),
+                ("seg", c_void_p), ("bin_of", c_void_p), ("n_bins", c_uint32), ("stats", c_void_p)]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -235,6 +249,9 @@ def lib():
         "cndp_pcb_count": (c_int, [c_void_p]),
         "cndp_pcb_lookup": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
         "cndp_gpu_udp_input": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(L4Io), c_void_p]),
+        # cndp_tcp.h
+        "cndp_pcb_lookup_indexed": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+        "cndp_gpu_tcp_input": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(TcpIo), c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -256,10 +273,10 @@ def exported_symbols():
     return sorted(set(n for n in names if not n.endswith("_fn_t")))
 
 
-def l4_exported_symbols():
-    """Names include/cndp_l4.h declares."""
+def l4_exported_symbols(header: str = "cndp_l4.h"):
+    """Names include/cndp_l4.h (or another header of include/) declares."""
     import re
-    with open(os.path.join(os.path.dirname(HERE), "include", "cndp_l4.h")) as f:
+    with open(os.path.join(os.path.dirname(HERE), "include", header)) as f:
         txt = f.read()
     return sorted(set(re.findall(r"^[A-Za-z_][\w \*]*?\b(cndp_\w+)\s*\(", txt, re.M)))
 

@@ -497,3 +497,97 @@ def udp_socket_frames(n: int, sockets, foreign=((0xC6120001, 9),), seed: int = 1
     slab = torch.from_numpy(buf).to(device)
     return Frames(slab, n, stride=stride, data_off=data_off, lengths=torch.from_numpy(lens),
                   offsets=torch.from_numpy(offs).to(device) if layout == "offsets" else None)
+
+
+def tcp_socket_frames(n: int, pairs, seed: int = 1, payload_lens=(0, 1, 18, 64), ihl=(5,),
+                      vlan_frac: float = 0.0, cksum=("ok",), data_off=(5,),
+                      flags=(0x10, 0x02, 0x12, 0x11, 0x18, 0x03, 0xD0), layout: str = "packed",
+                      slot: int = 128, align: int = 1, device="cpu") -> Frames:
+    """TCP segments addressed to local sockets (the traffic tcp_input terminates).
+
+    pairs: [((local address, local port), (foreign address, foreign port))],
+    addresses as host-order integers; frame i carries a drawn pair's 4-tuple.
+    Per frame, drawn from the given tuples with a seeded generator: the payload
+    length, the IPv4 IHL (5..15, options are NOPs), the TCP flags byte, the
+    data offset, and how the checksum is set -- "ok" (0 sent as 0xffff), "bad"
+    (that value + 1) or "zero" (a valid segment whose checksum field is all
+    zero: the urgent pointer is chosen so that the sum comes out that way).
+    A data_off entry is d (the header holds max(d, 5) words, TCP options are
+    NOPs, the field says d: d < 5 is the reference's rx_badoff) or (d, words)
+    (the field says d, the header holds `words` words: a d past the end of a
+    short segment).  Sequence and acknowledgement numbers and the window are
+    drawn too.  vlan_frac, layout, slot, align and Frames.lengths as in
+    udp_socket_frames."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    pick = lambda seq: [seq[k] for k in rng.integers(0, len(seq), n)]  # noqa: E731
+    prs, pls, ihls, cks = pick(list(pairs)), pick(list(payload_lens)), pick(list(ihl)), pick(list(cksum))
+    doffs, fls = pick(list(data_off)), pick(list(flags))
+    tagged = rng.random(n) < vlan_frac
+    frames = []
+    for i in range(n):
+        hl, pl = ihls[i] * 4, pls[i]
+        (dst, dport), (src, sport) = prs[i]
+        d, words = doffs[i] if isinstance(doffs[i], tuple) else (doffs[i], max(doffs[i], 5))
+        tot = hl + 4 * words + pl
+        ip = bytearray(hl)
+        ip[0] = 0x40 | ihls[i]
+        ip[2:4] = tot.to_bytes(2, "big")
+        ip[4:6] = int(rng.integers(0, 65536)).to_bytes(2, "big")
+        ip[8], ip[9] = 64, 6
+        ip[12:16], ip[16:20] = src.to_bytes(4, "big"), dst.to_bytes(4, "big")
+        for k in range(20, hl):
+            ip[k] = 1
+        s = sum(int.from_bytes(ip[k:k + 2], "big") for k in range(0, hl, 2))
+        s = (s >> 16) + (s & 0xFFFF)
+        s = (s >> 16) + (s & 0xFFFF)
+        ip[10:12] = ((~s) & 0xFFFF).to_bytes(2, "big")
+        tcp = bytearray(sport.to_bytes(2, "big") + dport.to_bytes(2, "big")
+                        + int(rng.integers(0, 1 << 32)).to_bytes(4, "big")
+                        + int(rng.integers(0, 1 << 32)).to_bytes(4, "big")
+                        + bytes([(d & 0xF) << 4 | int(rng.integers(0, 16)), fls[i]])
+                        + int(rng.integers(0, 65536)).to_bytes(2, "big") + b"\0\0"
+                        + int(rng.integers(0, 65536)).to_bytes(2, "big")
+                        + b"\x01" * (4 * words - 20) + rng.integers(0, 256, pl, dtype=np.uint8).tobytes())
+
+        def csum():
+            data = bytes(ip[12:20]) + bytes([0, 6]) + len(tcp).to_bytes(2, "big") + bytes(tcp)
+            data += b"\0" * (len(data) & 1)
+            c = sum(int.from_bytes(data[k:k + 2], "big") for k in range(0, len(data), 2))
+            while c >> 16:
+                c = (c >> 16) + (c & 0xFFFF)
+            return c
+        if cks[i] == "zero":
+            tcp[18:20] = b"\0\0"
+            tcp[18:20] = (0xFFFF - csum()).to_bytes(2, "big")   # the sum is 0xffff with the field at zero
+        else:
+            c = ((~csum()) & 0xFFFF) or 0xFFFF
+            if cks[i] == "bad":
+                c = (c + 1) & 0xFFFF or 1
+            tcp[16:18] = c.to_bytes(2, "big")
+        eth = bytes.fromhex("020000000001020000000002") + (b"\x81\x00\x00\x05" if tagged[i] else b"") + b"\x08\x00"
+        frames.append(eth + bytes(ip) + bytes(tcp))
+    lens = np.array([len(f) for f in frames], np.int64)
+    data_off_b = 0
+    if layout == "packed":
+        stride, offs = slot, np.arange(n, dtype=np.int64) * slot
+        total = n * slot
+    elif layout == "umem":
+        stride, data_off_b, offs = 2048, 256, np.arange(n, dtype=np.int64) * 2048
+        total = n * 2048
+    else:
+        stride, offs, at = 0, np.zeros(n, np.int64), 0
+        for i in range(n):
+            at = (at + align - 1) // align * align
+            offs[i] = at
+            at += int(lens[i])
+        total = at
+    buf = np.zeros(max(total, 1), np.uint8)
+    for i, f in enumerate(frames):
+        room = slot if layout == "packed" else (2048 - 256 if layout == "umem" else len(f))
+        f = f[:room]
+        o = int(offs[i]) + data_off_b
+        buf[o:o + len(f)] = np.frombuffer(f, np.uint8)
+    slab = torch.from_numpy(buf).to(device)
+    return Frames(slab, n, stride=stride, data_off=data_off_b, lengths=torch.from_numpy(lens),
+                  offsets=torch.from_numpy(offs).to(device) if layout == "offsets" else None)
