@@ -31,6 +31,7 @@
 #include "fib_internal.h"
 #include "node_internal.h"
 #include "../../include/cndp_gpu.h"
+#include "../../include/cndp_l4.h" // CNDP_PCB_MAX_ENTRIES
 
 #define CNDP_VERSION "cndp_amd 0.1 (gfx950)"
 
@@ -4278,13 +4279,16 @@ __global__ __launch_bounds__(256) void k_bin_ids(uint32_t mode, const uint32_t *
 
 #define PART_TILE 1024u
 #define PART_THREADS 256u
+// one bin a PCB index: the L4 stages' bin_of is this partition's input
+static_assert(CNDP_PART_BINS_MAX >= CNDP_PCB_MAX_ENTRIES, "every PCB table's bins must be partitionable");
+static_assert(CNDP_PART_BINS_MAX >= CNDP_BINS_MAX, "the classify bins must be partitionable");
 
 // pass 1: per-tile histogram, stored bin-major: hist[bin * tiles + tile]
 __global__ __launch_bounds__(PART_THREADS) void k_part_hist(const uint16_t *__restrict__ bin_of,
                                                             uint32_t n, uint32_t nbt,
                                                             uint32_t tiles, uint32_t *hist)
 {
-    __shared__ uint32_t h[CNDP_BINS_MAX + 2];
+    __shared__ uint32_t h[CNDP_PART_BINS_MAX + 2];
     for (uint32_t k = threadIdx.x; k < nbt; k += PART_THREADS)
         h[k] = 0;
     __syncthreads();
@@ -4356,7 +4360,7 @@ __global__ __launch_bounds__(PART_THREADS) void k_part_scatter(const uint16_t *_
                                                                const uint32_t *__restrict__ off,
                                                                uint32_t *__restrict__ order)
 {
-    __shared__ uint32_t cur[CNDP_BINS_MAX + 2];
+    __shared__ uint32_t cur[CNDP_PART_BINS_MAX + 2];
     for (uint32_t k = threadIdx.x; k < nbt; k += PART_THREADS)
         cur[k] = off[(uint64_t)k * tiles + blockIdx.x];
     __syncthreads();
@@ -6686,7 +6690,7 @@ extern "C" int cndp_gpu_bin_partition(cndp_gpu_ctx_t *c, const uint16_t *bin_of,
                                       uint32_t n_bins, uint32_t *bin_start, uint32_t *order,
                                       void *stream)
 {
-    if (!c || !bin_start || n_bins > CNDP_BINS_MAX || (n && (!bin_of || !order)))
+    if (!c || !bin_start || n_bins > CNDP_PART_BINS_MAX || (n && (!bin_of || !order)))
         return -EINVAL;
     int r = set_device(c->dev);
     if (r)
@@ -6694,6 +6698,8 @@ extern "C" int cndp_gpu_bin_partition(cndp_gpu_ctx_t *c, const uint16_t *bin_of,
     const uint32_t nbt = n_bins + 2;
     const uint32_t tiles = n ? blocks_for(n, PART_TILE) : 1;
     const size_t need = (size_t)nbt * tiles;
+    if (need > UINT32_MAX) // k_part_scan indexes the histogram with 32 bits
+        return -EINVAL;
     if (need > c->part_cap) {
         if (c->d_part)
             HIP_TRY(hipFree(c->d_part));

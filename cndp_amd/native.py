@@ -34,6 +34,7 @@ CNDP_EDGE_CLS_DROP = 0xFF
 CNDP_RSS_KEY_LEN = 40
 CNDP_RETA_MAX = 512
 CNDP_BINS_MAX = 1024
+CNDP_PART_BINS_MAX = 4096
 CNDP_FRAMES_CACHED = 1
 CNDP_TUNE_NT, CNDP_TUNE_UNROLL, CNDP_TUNE_BLOCKS_PER_CU, CNDP_TUNE_TILE, CNDP_TUNE_DIR16 = 1, 2, 3, 4, 5
 CNDP_TUNE_CNET_TILE = 6

@@ -61,7 +61,8 @@ extern "C" {
 #define CNDP_EDGE_CLS_DROP 0xFFu /* l3fwd: pkt_cls sent the packet to pkt_drop */
 #define CNDP_RSS_KEY_LEN 40u
 #define CNDP_RETA_MAX 512u
-#define CNDP_BINS_MAX 1024u
+#define CNDP_BINS_MAX 1024u       /* classify counters (cndp_batch.bins) and cndp_gpu_bin_ids */
+#define CNDP_PART_BINS_MAX 4096u  /* cndp_gpu_bin_partition; >= CNDP_PCB_MAX_ENTRIES (cndp_l4.h) */
 
 typedef struct cndp_gpu_ctx cndp_gpu_ctx_t;
 
@@ -361,7 +362,11 @@ int cndp_gpu_frames_free(void *dptr);
 /* Stable partition of packet indices by bin (the per-edge streams a graph
  * walk would build): bin_of[i] in [0, n_bins+2) (device), outputs
  * bin_start[n_bins+3] (exclusive prefix, device) and order[n] (device).
- * The result equals a stable counting sort of i by bin_of[i]. */
+ * The result equals a stable counting sort of i by bin_of[i].  n_bins <=
+ * CNDP_PART_BINS_MAX -- every PCB table's bins (cndp_l4.h, cndp_tcp.h) and
+ * every classify n_bins -- and (n_bins + 2) * ceil(n / 1024) < 2^32, else
+ * -EINVAL, as for a NULL bin_start or, with n > 0, a NULL bin_of or order.
+ * n == 0 writes bin_start (all zero) and leaves order alone. */
 int cndp_gpu_bin_partition(cndp_gpu_ctx_t *ctx, const uint16_t *bin_of, uint32_t n,
                            uint32_t n_bins, uint32_t *bin_start, uint32_t *order, void *stream);
 

@@ -105,7 +105,9 @@ struct cndp_l4_io {
     uint16_t *payload_off; /* l2_len + l3_len + l4_len on chnl_recv (udp_input.c:115), else 0 */
     uint16_t *bin_of;      /* the PCB index on chnl_recv, n_bins for every drop, n_bins + 1
                             * for the rest: cndp_gpu_bin_partition's input */
-    uint32_t n_bins;       /* >= cndp_pcb_count(tbl) and <= 65533 when bin_of is given */
+    uint32_t n_bins;       /* >= cndp_pcb_count(tbl) and <= 65533 when bin_of is given;
+                            * cndp_gpu_bin_partition takes n_bins <= CNDP_PART_BINS_MAX
+                            * (every table's count fits) and returns -EINVAL above it */
     uint64_t *stats;       /* [4], CNDP_L4_STAT_*, accumulated (+=) */
 };
 

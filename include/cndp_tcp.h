@@ -87,7 +87,9 @@ struct cndp_tcp_io {
     uint16_t *bin_of;   /* the PCB index on SEGMENT, n_bins for every drop, n_bins + 1 for the
                          * rest: cndp_gpu_bin_partition then gives per-connection lists in
                          * arrival order */
-    uint32_t n_bins;    /* >= cndp_pcb_count(tbl) and <= 65533 when bin_of is given */
+    uint32_t n_bins;    /* >= cndp_pcb_count(tbl) and <= 65533 when bin_of is given;
+                         * cndp_gpu_bin_partition takes n_bins <= CNDP_PART_BINS_MAX (every
+                         * table's count fits) and returns -EINVAL above it */
     uint64_t *stats;    /* [CNDP_TCP_NSTATS], CNDP_TCP_STAT_*, accumulated (+=) */
 };
 
