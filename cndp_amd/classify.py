@@ -336,6 +336,34 @@ class Classifier:
         tcp["n_bins"] = n_bins
         return tcp
 
+    def ip4_forward(self, frames, out: dict, table, burst: int = 256, sel=None, n_bins: int | None = None,
+                    stream: int | None = None, fwd: dict | None = None) -> dict:
+        """ip4_forward (cndp_gpu_ip4_forward, include/cndp_fwd.h) over the frames
+        a cnet classify of `frames` sent to ip4_input's forward edge, rewriting
+        the slab in place: `out` is that classify's output dict (nh, rxmeta and,
+        unless `sel` is given, ptype), `table` a FwdTable, `burst` the graph
+        burst the node's 4-wide / 1-wide loops run over.  Returns the stage's
+        outputs as tensors (fwd_edge, arp_idx, bin_of, stats; stats accumulates
+        when a previous result is passed back as `fwd`)."""
+        import torch
+        from .fwd import alloc_fwd_outputs
+        dev = frames.slab.device
+        if n_bins is None:
+            n_bins = max(1, table.max_netif() + 1)
+        if fwd is None:
+            fwd = alloc_fwd_outputs(frames.n, dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        b = self.batch(frames, N.CNDP_MODE_CNET, out)
+        io = N.FwdIo()
+        io.sel = self._ptr(sel)
+        io.fwd_edge, io.arp_idx, io.bin_of = self._ptr(fwd.get("fwd_edge")), self._ptr(fwd.get("arp_idx")), self._ptr(fwd.get("bin_of"))
+        io.n_bins, io.stats = n_bins, self._ptr(fwd.get("stats"))
+        N.check(self._L.cndp_gpu_ip4_forward(self.h, table.h, ctypes.byref(b), burst, ctypes.byref(io),
+                                             stream or None), "cndp_gpu_ip4_forward")
+        fwd["n_bins"] = n_bins
+        return fwd
+
     def bin_ids(self, mode: int, out: dict, n: int, n_bins: int, stream: int | None = None):
         import torch
         dev = out["queue"].device

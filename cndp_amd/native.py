@@ -1,6 +1,6 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
-include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h and
-include/cndp_tcp.h).
+include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
+include/cndp_tcp.h and include/cndp_fwd.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -84,6 +84,14 @@ CNDP_TCP_INPUT_PKT_DROP, CNDP_TCP_INPUT_SEGMENT, CNDP_TCP_INPUT_PKT_PUNT = 0, 1,
  CNDP_TCP_STAT_RSVD) = range(5)
 CNDP_TCP_NSTATS = 5
 
+# cndp_fwd.h
+CNDP_FWD_OBJS_MAX = 1 << 24
+CNDP_FWD_NETIFS = 256
+CNDP_FWD_NONE = 0xFFFFFFFF
+CNDP_FWD_EDGE_PKT_DROP, CNDP_FWD_EDGE_ARP_REQUEST, CNDP_FWD_EDGE_OUTPUT = 0, 1, 2
+CNDP_FWD_EDGE_NONE = 0xFFFF
+CNDP_FWD_STAT_DIRECT, CNDP_FWD_STAT_GATEWAY, CNDP_FWD_STAT_ARP_REQUEST = 0, 1, 2
+
 
 def CNDP_L4_EDGE(node: int, e: int) -> int:
     return (node << 4) | e
@@ -145,6 +153,22 @@ class TcpIo(Structure):
     """struct cndp_tcp_io (cndp_tcp.h)."""
     _fields_ = [("sel", c_void_p), ("l4edge", c_void_p), ("pcb", c_void_p), ("ports", c_void_p),
                 ("seg", c_void_p), ("bin_of", c_void_p), ("n_bins", c_uint32), ("stats", c_void_p)]
+
+
+class FwdArp(Structure):
+    """struct cndp_fwd_arp (cndp_fwd.h)."""
+    _fields_ = [("netif_idx", c_uint16), ("ha", c_uint8 * 6)]
+
+
+class FwdRt(Structure):
+    """struct cndp_fwd_rt (cndp_fwd.h)."""
+    _fields_ = [("gateway", c_uint32), ("netif_idx", c_uint16)]
+
+
+class FwdIo(Structure):
+    """struct cndp_fwd_io (cndp_fwd.h)."""
+    _fields_ = [("sel", c_void_p), ("fwd_edge", c_void_p), ("arp_idx", c_void_p), ("bin_of", c_void_p),
+                ("n_bins", c_uint32), ("stats", c_void_p)]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -253,6 +277,17 @@ def lib():
         # cndp_tcp.h
         "cndp_pcb_lookup_indexed": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
         "cndp_gpu_tcp_input": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(TcpIo), c_void_p]),
+        # cndp_fwd.h
+        "cndp_fwd_create": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, POINTER(c_void_p)]),
+        "cndp_fwd_free": (None, [c_void_p]),
+        "cndp_fwd_arp_set": (c_int, [c_void_p, c_uint32, POINTER(FwdArp)]),
+        "cndp_fwd_arp_clear": (c_int, [c_void_p, c_uint32]),
+        "cndp_fwd_rt_set": (c_int, [c_void_p, c_uint32, POINTER(FwdRt)]),
+        "cndp_fwd_rt_clear": (c_int, [c_void_p, c_uint32]),
+        "cndp_fwd_netif_set": (c_int, [c_void_p, c_uint32, c_void_p]),
+        "cndp_fwd_max_netif": (c_int, [c_void_p]),
+        "cndp_fwd_lookup": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+        "cndp_gpu_ip4_forward": (c_int, [c_void_p, c_void_p, POINTER(Batch), c_uint32, POINTER(FwdIo), c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
