@@ -364,6 +364,39 @@ class Classifier:
         fwd["n_bins"] = n_bins
         return fwd
 
+    def ip4_output(self, frames, fwd_table, pcb_table, pcb, faddr, laddr, ports, length, mode: int = N.CNDP_TX_UDP,
+                   sel=None, n_bins: int | None = None, tx: dict | None = None, stream: int | None = None) -> dict:
+        """udp_output + ip4_output (cndp_gpu_ip4_output, include/cndp_tx.h) over
+        the transmit buffers `frames` describes (stride / offsets, data_off =
+        the headroom), writing the headers in place in front of each payload.
+        pcb, faddr, laddr, ports (fport | lport << 16; None in CNDP_TX_IP4
+        mode) are int32 tensors, length an int16 tensor, sel a uint8 tensor or
+        None for all; `fwd_table` a FwdTable, `pcb_table` a PcbTable.  Returns
+        the stage's outputs as tensors (tx_edge, bin_of, stats; stats
+        accumulates when a previous result is passed back as `tx`)."""
+        import torch
+        from .tx import alloc_tx_outputs
+        dev = frames.slab.device
+        if n_bins is None:
+            n_bins = max(1, fwd_table.max_netif() + 1)
+        if tx is None:
+            tx = alloc_tx_outputs(frames.n, dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        b = N.Batch()
+        b.mode, b.n, b.slab, b.slab_len = N.CNDP_MODE_CNET, frames.n, frames.slab.data_ptr(), frames.slab.numel()
+        b.stride, b.data_off = frames.stride, frames.data_off
+        b.offsets = frames.offsets.data_ptr() if frames.offsets is not None else None
+        io = N.TxIo()
+        io.sel, io.pcb, io.faddr, io.laddr = self._ptr(sel), self._ptr(pcb), self._ptr(faddr), self._ptr(laddr)
+        io.ports, io.len = self._ptr(ports), self._ptr(length)
+        io.tx_edge, io.bin_of = self._ptr(tx.get("tx_edge")), self._ptr(tx.get("bin_of"))
+        io.n_bins, io.stats = n_bins, self._ptr(tx.get("stats"))
+        N.check(self._L.cndp_gpu_ip4_output(self.h, fwd_table.h, pcb_table.h, ctypes.byref(b), mode, ctypes.byref(io),
+                                            stream or None), "cndp_gpu_ip4_output")
+        tx["n_bins"] = n_bins
+        return tx
+
     def bin_ids(self, mode: int, out: dict, n: int, n_bins: int, stream: int | None = None):
         import torch
         dev = out["queue"].device

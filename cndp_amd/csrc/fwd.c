@@ -53,6 +53,8 @@ void cndp_fwd_free(cndp_fwd_tbl_t *t)
         return;
     if (t->dev && t->dev_release)
         t->dev_release(t->dev);
+    if (t->xdev && t->xdev_release)
+        t->xdev_release(t->xdev);
     pthread_mutex_destroy(&t->lock);
     free(t->img);
     free(t);

@@ -37,6 +37,13 @@ struct cndp_fwd_tbl {
     uint32_t nif_refs[CNDP_FWD_NETIFS]; /* objects set per netif_idx */
     void *dev;                          /* the device mirror's state, owned by cndp_fwd.hip */
     void (*dev_release)(void *dev);
+    /* transmit side (include/cndp_tx.h), kept by tx.c */
+    uint16_t ident[CNDP_FWD_NETIFS];    /* the netifs' ip_ident, host copy */
+    int ident_host_new;                 /* set on the host since the device copy was written */
+    int ident_dev_new;                  /* a GPU call advanced the device copy since the last read-back */
+    void *xdev;                         /* the transmit stage's device state, owned by cndp_tx.hip */
+    void (*xdev_release)(void *xdev);
+    int (*xdev_ident_pull)(struct cndp_fwd_tbl *t); /* lock held: wait, read the counters back */
 };
 
 static inline uint32_t *fwd_arp(const struct cndp_fwd_tbl *t) { return t->img + FWD_IMG_HDR; }

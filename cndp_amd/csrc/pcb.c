@@ -55,7 +55,11 @@ void cndp_pcb_free(cndp_pcb_tbl_t *t)
         t->dev_release(t->dev);
     if (t->tdev && t->tdev_release)
         t->tdev_release(t->tdev);
+    if (t->xdev && t->xdev_release)
+        t->xdev_release(t->xdev);
     pthread_mutex_destroy(&t->lock);
+    free(t->txa);
+    free(t->ximg);
     free(t->vec);
     free(t->closed);
     free(t->img);

@@ -58,6 +58,13 @@ struct cndp_pcb_tbl {
     uint64_t timg_gen;      /* gen the TCP image was built from (0 = never) */
     void *tdev;             /* the TCP stage's device mirror, owned by cndp_tcp.hip */
     void (*tdev_release)(void *tdev);
+    /* transmit side (include/cndp_tx.h), kept by tx.c */
+    uint8_t *txa;           /* per entry: tos, ttl, ip_proto; allocated on first use */
+    uint32_t txa_n;         /* entries of the vector given their defaults so far */
+    uint32_t *ximg;         /* transmit image (tx_internal.h), host copy */
+    uint64_t ximg_gen;      /* gen the transmit image was built from (0 = never) */
+    void *xdev;             /* the transmit stage's device mirror, owned by cndp_tx.hip */
+    void (*xdev_release)(void *xdev);
 };
 
 /* Call with tbl->lock held: bring tbl->img up to date.  0 or -ENOMEM. */

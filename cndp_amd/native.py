@@ -1,6 +1,6 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
-include/cndp_tcp.h and include/cndp_fwd.h).
+include/cndp_tcp.h, include/cndp_fwd.h and include/cndp_tx.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -92,6 +92,14 @@ CNDP_FWD_EDGE_PKT_DROP, CNDP_FWD_EDGE_ARP_REQUEST, CNDP_FWD_EDGE_OUTPUT = 0, 1, 
 CNDP_FWD_EDGE_NONE = 0xFFFF
 CNDP_FWD_STAT_DIRECT, CNDP_FWD_STAT_GATEWAY, CNDP_FWD_STAT_ARP_REQUEST = 0, 1, 2
 
+# cndp_tx.h
+CNDP_TX_UDP, CNDP_TX_IP4 = 0, 1
+CNDP_TX_EDGE_PKT_DROP, CNDP_TX_EDGE_ARP_REQUEST, CNDP_TX_EDGE_OUTPUT = 0, 1, 2
+CNDP_TX_EDGE_NONE = 0xFFFF
+(CNDP_TX_STAT_SENT, CNDP_TX_STAT_ARP_REQUEST, CNDP_TX_STAT_DROP_HEADROOM, CNDP_TX_STAT_DROP_NOROUTE,
+ CNDP_TX_STAT_DROP_PROTO, CNDP_TX_STAT_CKSUM) = range(6)
+CNDP_TX_NSTATS = 6
+
 
 def CNDP_L4_EDGE(node: int, e: int) -> int:
     return (node << 4) | e
@@ -168,6 +176,18 @@ class FwdRt(Structure):
 class FwdIo(Structure):
     """struct cndp_fwd_io (cndp_fwd.h)."""
     _fields_ = [("sel", c_void_p), ("fwd_edge", c_void_p), ("arp_idx", c_void_p), ("bin_of", c_void_p),
+                ("n_bins", c_uint32), ("stats", c_void_p)]
+
+
+class PcbTx(Structure):
+    """struct cndp_pcb_tx (cndp_tx.h)."""
+    _fields_ = [("tos", c_uint8), ("ttl", c_uint8), ("ip_proto", c_uint8)]
+
+
+class TxIo(Structure):
+    """struct cndp_tx_io (cndp_tx.h)."""
+    _fields_ = [("sel", c_void_p), ("pcb", c_void_p), ("faddr", c_void_p), ("laddr", c_void_p),
+                ("ports", c_void_p), ("len", c_void_p), ("tx_edge", c_void_p), ("bin_of", c_void_p),
                 ("n_bins", c_uint32), ("stats", c_void_p)]
 
 
@@ -288,6 +308,15 @@ def lib():
         "cndp_fwd_max_netif": (c_int, [c_void_p]),
         "cndp_fwd_lookup": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
         "cndp_gpu_ip4_forward": (c_int, [c_void_p, c_void_p, POINTER(Batch), c_uint32, POINTER(FwdIo), c_void_p]),
+        # cndp_tx.h
+        "cndp_pcb_tx_set": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
+        "cndp_pcb_tx_get": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
+        "cndp_fwd_netif_ident_set": (c_int, [c_void_p, c_uint32, c_uint16]),
+        "cndp_fwd_netif_ident_get": (c_int, [c_void_p, c_uint32, POINTER(c_uint16)]),
+        "cndp_gpu_ip4_output": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(Batch), c_uint32, POINTER(TxIo),
+                                        c_void_p]),
+        "cndp_tx_output_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_uint64, c_void_p,
+                                        c_uint32, c_uint32, POINTER(TxIo)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
