@@ -336,6 +336,32 @@ class Classifier:
         tcp["n_bins"] = n_bins
         return tcp
 
+    def tcp_segment(self, frames, out: dict, tcb_table, tcp: dict, now: int = 0, sel=None,
+                    stream: int | None = None, seg: dict | None = None) -> dict:
+        """tcp_do_options and the header-prediction triage (cndp_gpu_tcp_segment,
+        include/cndp_tcb.h) over the frames tcp_input left on its SEGMENT edge.
+        `out` is the cnet classify's output dict (rxmeta), `tcb_table` a TcbTable,
+        `tcp` tcp_input's result of the same batch (l4edge, pcb, seg; none of
+        them is written), `now` the stack's timer ticks.  With `sel` (a uint8
+        tensor) it decides which frames are taken instead of l4edge.  Returns the
+        stage's outputs as tensors (opt, verdict, stats; stats accumulates when
+        a previous result is passed back as `seg`)."""
+        import torch
+        from .l4 import alloc_tcpseg_outputs
+        dev = frames.slab.device
+        if seg is None:
+            seg = alloc_tcpseg_outputs(frames.n, dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        b = self.batch(frames, N.CNDP_MODE_CNET, out)
+        io = N.TcpSegIo()
+        io.sel = self._ptr(sel)
+        io.l4edge, io.pcb, io.seg = self._ptr(tcp.get("l4edge")), self._ptr(tcp.get("pcb")), self._ptr(tcp.get("seg"))
+        io.opt, io.verdict, io.stats = self._ptr(seg.get("opt")), self._ptr(seg.get("verdict")), self._ptr(seg.get("stats"))
+        N.check(self._L.cndp_gpu_tcp_segment(self.h, tcb_table.h, ctypes.byref(b), ctypes.byref(io),
+                                             now & 0xFFFFFFFF, stream or None), "cndp_gpu_tcp_segment")
+        return seg
+
     def ip4_forward(self, frames, out: dict, table, burst: int = 256, sel=None, n_bins: int | None = None,
                     stream: int | None = None, fwd: dict | None = None) -> dict:
         """ip4_forward (cndp_gpu_ip4_forward, include/cndp_fwd.h) over the frames

@@ -1,6 +1,7 @@
-"""UDP and TCP socket demux (include/cndp_l4.h, include/cndp_tcp.h): the PCB
-table udp_input / tcp_input look frames up in, and the output arrays of
-Classifier.udp_input and Classifier.tcp_input.
+"""UDP and TCP socket demux (include/cndp_l4.h, include/cndp_tcp.h,
+include/cndp_tcb.h): the PCB table udp_input / tcp_input look frames up in, the
+TCB table tcp_segment reads, and the output arrays of Classifier.udp_input,
+Classifier.tcp_input and Classifier.tcp_segment.
 
     tbl = PcbTable(512)
     i = tbl.add(laddr="10.4.0.7", lport=5000, cksum=True)    # a bound listener
@@ -17,6 +18,13 @@ ip4_proto's tcp edge:
     tbl.set_flags(tcp_enabled=True)
     l4 = c.udp_input(frames, out, tbl)
     t = c.tcp_input(frames, out, tcp, l4=l4)                 # l4edge (in place), pcb, seg, bin_of, ...
+
+Behind it, option parsing and the header-prediction triage (include/cndp_tcb.h)
+against the connections' TCB snapshots, kept in a TcbTable beside the TCP table:
+
+    tcbs = TcbTable(tcp)
+    tcbs.set(1, state=N.CNDP_TCPS_ESTABLISHED, rcv_nxt=..., snd_una=..., ...)
+    s = c.tcp_segment(frames, out, tcbs, t, now=ticks)       # opt, verdict, stats
 
 Addresses and ports are kept in network order, as the u32 / u16 a
 little-endian host loads from the frame; add() and lookup keys take host
@@ -152,3 +160,109 @@ def alloc_tcp_outputs(n: int, device, l4edge=None) -> dict:
 def seg_records(seg) -> np.ndarray:
     """The seg tensor of Classifier.tcp_input on the host, as SEG_DT records."""
     return np.ascontiguousarray(seg.cpu().numpy()).view(SEG_DT).reshape(-1)
+
+
+# ---------------------------------------------------------------------------
+# TCP option parse and header-prediction triage (include/cndp_tcb.h)
+# ---------------------------------------------------------------------------
+# struct cndp_tcp_opt
+OPT_DT = np.dtype([("ts_val", "<u4"), ("ts_ecr", "<u4"), ("wnd", "<u4"), ("mss", "<u2"), ("sflags", "<u2")])
+TCB_FIELDS = ("rcv_nxt", "snd_una", "snd_nxt", "snd_max", "snd_wnd", "snd_cwnd", "ts_recent", "last_ack_sent",
+              "rcv_space", "max_mss", "state", "snd_scale", "flags")
+
+
+class TcbTable:
+    """cndp_tcb_* (include/cndp_tcb.h): the per-PCB snapshot of the connection
+    variables tcp_do_options and the header-prediction tests read, beside the
+    PcbTable that holds the TCP vector (which must stay open while this is).
+
+        tcbs = TcbTable(tcp)
+        tcbs.set(i, state=N.CNDP_TCPS_ESTABLISHED, rcv_nxt=..., snd_una=..., ...)
+        t = c.tcp_input(frames, out, tcp, l4=l4)
+        s = c.tcp_segment(frames, out, tcbs, t, now=ticks)        # opt, verdict, stats
+    """
+
+    def __init__(self, pcb_table: PcbTable):
+        self._L = N.lib()
+        self.pcb_table = pcb_table
+        h = ctypes.c_void_p()
+        N.check(self._L.cndp_tcb_tbl_create(pcb_table.h, ctypes.byref(h)), "cndp_tcb_tbl_create")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self._L.cndp_tcb_tbl_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_raw(self, idx: int, **fields) -> int:
+        """cndp_tcb_set; returns its result (0 or -errno).  Fields not given are 0."""
+        t = N.Tcb()
+        for k, v in fields.items():
+            if k not in TCB_FIELDS:
+                raise TypeError(f"struct cndp_tcb has no field {k!r}")
+            setattr(t, k, int(v))
+        return self._L.cndp_tcb_set(self.h, idx, ctypes.byref(t))
+
+    def set(self, idx: int, **fields) -> None:
+        N.check(self.set_raw(idx, **fields), "cndp_tcb_set")
+
+    def clear(self, idx: int) -> int:
+        """cndp_tcb_clear; returns its result (0 or -errno)."""
+        return self._L.cndp_tcb_clear(self.h, idx)
+
+    def get(self, idx: int):
+        """The snapshot as a dict, or None when the index has no TCB."""
+        t = N.Tcb()
+        r = self._L.cndp_tcb_get(self.h, idx, ctypes.byref(t))
+        if r == -2:
+            return None
+        N.check(r, "cndp_tcb_get")
+        return {k: int(getattr(t, k)) for k in TCB_FIELDS}
+
+    def segment_host(self, slab: np.ndarray, n: int, rxmeta, pcb, seg, now: int, l4edge=None, sel=None,
+                     stride: int = 0, offsets=None, data_off: int = 0, stats=None) -> dict:
+        """cndp_tcp_segment_host over host arrays: the stage's rule on the
+        calling thread.  Returns opt (OPT_DT), verdict (uint8) and stats
+        (uint64[CNDP_TCPSEG_NSTATS], accumulated into `stats` when given)."""
+        keep = [np.ascontiguousarray(slab, np.uint8), np.ascontiguousarray(rxmeta, np.uint32),
+                np.ascontiguousarray(pcb, np.uint32), np.ascontiguousarray(seg, SEG_DT)]
+        opt, verdict = np.zeros(max(n, 1), OPT_DT), np.zeros(max(n, 1), np.uint8)
+        st = np.zeros(N.CNDP_TCPSEG_NSTATS, np.uint64) if stats is None else np.array(stats, np.uint64)
+        b = N.Batch()
+        b.mode, b.n, b.slab, b.slab_len = N.CNDP_MODE_CNET, n, keep[0].ctypes.data, len(keep[0])
+        b.stride, b.data_off, b.rxmeta = stride, data_off, keep[1].ctypes.data
+        if offsets is not None:
+            keep.append(np.ascontiguousarray(offsets, np.uint64))
+            b.offsets = keep[-1].ctypes.data
+        io = N.TcpSegIo()
+        for name, arr in (("sel", sel), ("l4edge", l4edge)):
+            if arr is not None:
+                keep.append(np.ascontiguousarray(arr, np.uint8))
+                setattr(io, name, keep[-1].ctypes.data)
+        io.pcb, io.seg, io.opt, io.verdict, io.stats = (keep[2].ctypes.data, keep[3].ctypes.data, opt.ctypes.data,
+                                                        verdict.ctypes.data, st.ctypes.data)
+        N.check(self._L.cndp_tcp_segment_host(self.h, now & 0xFFFFFFFF, ctypes.byref(b), ctypes.byref(io)),
+                "cndp_tcp_segment_host")
+        return {"opt": opt[:n], "verdict": verdict[:n], "stats": st}
+
+
+def alloc_tcpseg_outputs(n: int, device) -> dict:
+    """The output arrays of cndp_gpu_tcp_segment as torch tensors.  opt is an
+    (n, 4) int32 tensor, one 16-byte struct cndp_tcp_opt per row (opt_records()
+    views it as OPT_DT)."""
+    import torch
+    m = max(n, 1)
+    return {"opt": torch.empty((m, 4), dtype=torch.int32, device=device)[:n],
+            "verdict": torch.empty(m, dtype=torch.uint8, device=device)[:n],
+            "stats": torch.zeros(N.CNDP_TCPSEG_NSTATS, dtype=torch.int64, device=device)}
+
+
+def opt_records(opt) -> np.ndarray:
+    """The opt tensor of Classifier.tcp_segment on the host, as OPT_DT records."""
+    return np.ascontiguousarray(opt.cpu().numpy()).view(OPT_DT).reshape(-1)

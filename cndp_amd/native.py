@@ -1,6 +1,6 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
-include/cndp_tcp.h, include/cndp_fwd.h and include/cndp_tx.h).
+include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h and include/cndp_tx.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -84,6 +84,18 @@ CNDP_TCP_INPUT_PKT_DROP, CNDP_TCP_INPUT_SEGMENT, CNDP_TCP_INPUT_PKT_PUNT = 0, 1,
  CNDP_TCP_STAT_RSVD) = range(5)
 CNDP_TCP_NSTATS = 5
 
+# cndp_tcb.h
+(CNDP_TCPS_FREE, CNDP_TCPS_CLOSED, CNDP_TCPS_LISTEN, CNDP_TCPS_SYN_SENT, CNDP_TCPS_SYN_RCVD, CNDP_TCPS_ESTABLISHED,
+ CNDP_TCPS_CLOSE_WAIT, CNDP_TCPS_FIN_WAIT_1, CNDP_TCPS_CLOSING, CNDP_TCPS_LAST_ACK, CNDP_TCPS_FIN_WAIT_2,
+ CNDP_TCPS_TIME_WAIT) = range(12)
+CNDP_TCB_REASS_EMPTY = 1
+CNDP_SEG_TS_PRESENT, CNDP_SEG_MSS_PRESENT, CNDP_SEG_WS_PRESENT, CNDP_SEG_SACK_PERMIT = 0x8000, 0x4000, 0x2000, 0x1000
+CNDP_SEG_REQ_SCALE = 0x000F
+(CNDP_TCPSEG_NONE, CNDP_TCPSEG_RESET, CNDP_TCPSEG_CLOSED, CNDP_TCPSEG_BADOPT, CNDP_TCPSEG_SLOW,
+ CNDP_TCPSEG_PRED_ACK, CNDP_TCPSEG_PRED_DATA, CNDP_TCPSEG_PRED_NONE) = range(8)
+CNDP_TCPSEG_NSTATS = 8
+CNDP_TCPSEG_VERDICT, CNDP_TCPSEG_TS_UPDATE, CNDP_TCPSEG_FIRST = 0x0F, 0x40, 0x80
+
 # cndp_fwd.h
 CNDP_FWD_OBJS_MAX = 1 << 24
 CNDP_FWD_NETIFS = 256
@@ -161,6 +173,20 @@ class TcpIo(Structure):
     """struct cndp_tcp_io (cndp_tcp.h)."""
     _fields_ = [("sel", c_void_p), ("l4edge", c_void_p), ("pcb", c_void_p), ("ports", c_void_p),
                 ("seg", c_void_p), ("bin_of", c_void_p), ("n_bins", c_uint32), ("stats", c_void_p)]
+
+
+class Tcb(Structure):
+    """struct cndp_tcb (cndp_tcb.h)."""
+    _fields_ = [("rcv_nxt", c_uint32), ("snd_una", c_uint32), ("snd_nxt", c_uint32), ("snd_max", c_uint32),
+                ("snd_wnd", c_uint32), ("snd_cwnd", c_uint32), ("ts_recent", c_uint32),
+                ("last_ack_sent", c_uint32), ("rcv_space", c_uint32), ("max_mss", c_uint16), ("state", c_uint8),
+                ("snd_scale", c_uint8), ("flags", c_uint8), ("rsvd", c_uint8 * 7)]
+
+
+class TcpSegIo(Structure):
+    """struct cndp_tcpseg_io (cndp_tcb.h)."""
+    _fields_ = [("sel", c_void_p), ("l4edge", c_void_p), ("pcb", c_void_p), ("seg", c_void_p),
+                ("opt", c_void_p), ("verdict", c_void_p), ("stats", c_void_p)]
 
 
 class FwdArp(Structure):
@@ -297,6 +323,14 @@ def lib():
         # cndp_tcp.h
         "cndp_pcb_lookup_indexed": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
         "cndp_gpu_tcp_input": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(TcpIo), c_void_p]),
+        # cndp_tcb.h
+        "cndp_tcb_tbl_create": (c_int, [c_void_p, POINTER(c_void_p)]),
+        "cndp_tcb_tbl_destroy": (None, [c_void_p]),
+        "cndp_tcb_set": (c_int, [c_void_p, c_uint32, POINTER(Tcb)]),
+        "cndp_tcb_clear": (c_int, [c_void_p, c_uint32]),
+        "cndp_tcb_get": (c_int, [c_void_p, c_uint32, POINTER(Tcb)]),
+        "cndp_gpu_tcp_segment": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(TcpSegIo), c_uint32, c_void_p]),
+        "cndp_tcp_segment_host": (c_int, [c_void_p, c_uint32, POINTER(Batch), POINTER(TcpSegIo)]),
         # cndp_fwd.h
         "cndp_fwd_create": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, POINTER(c_void_p)]),
         "cndp_fwd_free": (None, [c_void_p]),
