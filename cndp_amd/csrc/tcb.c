@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/cndp_tcpout.h"
 #include "tcb_internal.h"
 
 #define EDGE_SEG CNDP_L4_EDGE(CNDP_L4_NODE_TCP_INPUT, CNDP_TCP_INPUT_SEGMENT)
@@ -42,6 +43,7 @@ void cndp_tcb_tbl_destroy(cndp_tcb_tbl_t *t)
         return;
     if (t->dev && t->dev_release)
         t->dev_release(t->dev);
+    free(t->kimg);
     pthread_mutex_destroy(&t->lock);
     free(t->img);
     free(t);
@@ -105,8 +107,9 @@ int cndp_tcb_set(cndp_tcb_tbl_t *t, uint32_t idx, const struct cndp_tcb *tcb)
         e[7] = tcb->last_ack_sent;
         e[8] = tcb->rcv_space;
         e[9] = tcb->max_mss | (uint32_t)tcb->state << 16 | (uint32_t)tcb->snd_scale << 24;
+        if (!(e[10] & TCB_PRESENT))
+            e[11] = 0; /* a fresh TCB: no transmit attributes; an existing one keeps them */
         e[10] = (tcb->flags & CNDP_TCB_REASS_EMPTY) | TCB_PRESENT;
-        e[11] = 0;
         touched(t, idx);
     }
     pthread_mutex_unlock(&t->lock);
@@ -157,6 +160,49 @@ int cndp_tcb_get(cndp_tcb_tbl_t *t, uint32_t idx, struct cndp_tcb *out)
             out->state = (uint8_t)(e[9] >> 16);
             out->snd_scale = (uint8_t)(e[9] >> 24);
             out->flags = (uint8_t)(e[10] & CNDP_TCB_REASS_EMPTY);
+        }
+    }
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+/* ---- transmit attributes (include/cndp_tcpout.h): word 11 of the entry ------ */
+#define TCB_TX_FLAGS (CNDP_TCBF_REQ_SCALE | CNDP_TCBF_RCVD_SCALE | CNDP_TCBF_REQ_TSTAMP | CNDP_TCBF_RCVD_TSTAMP)
+
+int cndp_tcb_tx_set(cndp_tcb_tbl_t *t, uint32_t idx, const struct cndp_tcb_tx *a)
+{
+    if (!t || !a)
+        return -EINVAL;
+    pthread_mutex_lock(&t->lock);
+    int r = slot_ok(t, idx);
+    if (!r) {
+        uint32_t *e = t->img + (size_t)idx * TCB_WORDS;
+        if (!(e[10] & TCB_PRESENT))
+            r = -ENOENT;
+        else {
+            e[11] = (a->tflags & TCB_TX_FLAGS) | (uint32_t)a->req_recv_scale << 8 | (uint32_t)a->rcv_scale << 16;
+            touched(t, idx);
+        }
+    }
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+int cndp_tcb_tx_get(cndp_tcb_tbl_t *t, uint32_t idx, struct cndp_tcb_tx *a)
+{
+    if (!t || !a)
+        return -EINVAL;
+    pthread_mutex_lock(&t->lock);
+    int r = idx >= tcb_reconcile(t) ? -EINVAL : 0;
+    if (!r) {
+        const uint32_t *e = t->img + (size_t)idx * TCB_WORDS;
+        if (!(e[10] & TCB_PRESENT))
+            r = -ENOENT;
+        else {
+            a->tflags = (uint8_t)e[11];
+            a->req_recv_scale = (uint8_t)(e[11] >> 8);
+            a->rcv_scale = (uint8_t)(e[11] >> 16);
+            a->rsvd = 0;
         }
     }
     pthread_mutex_unlock(&t->lock);

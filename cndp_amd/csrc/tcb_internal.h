@@ -20,7 +20,9 @@ extern "C" {
  *   [0] rcv_nxt  [1] snd_una  [2] snd_nxt  [3] snd_max
  *   [4] snd_wnd  [5] snd_cwnd  [6] ts_recent  [7] last_ack_sent
  *   [8] rcv_space  [9] max_mss | state << 16 | snd_scale << 24
- *   [10] flags | present << 8  [11] 0 */
+ *   [10] flags | present << 8
+ *   [11] the transmit attributes of include/cndp_tcpout.h, which the segment rule
+ *        below does not read: tflags | req_recv_scale << 8 | rcv_scale << 16 */
 #define TCB_WORDS 12u
 #define TCB_PRESENT 0x100u /* in word 10 */
 
@@ -34,6 +36,9 @@ struct cndp_tcb_tbl {
     uint64_t pcb_gen;     /* pcb->gen the deleted entries were last looked at (0 = never) */
     void *dev;            /* the device mirror's state, owned by cndp_tcb.hip */
     void (*dev_release)(void *dev);
+    /* transmit side (include/cndp_tcpout.h) */
+    uint32_t *kimg;       /* PCB key image (tcpout_internal.h), allocated on first use */
+    uint64_t kimg_gen;    /* pcb->gen the key image was built from (0 = never) */
 };
 
 /* Call with t->lock held: take the TCBs of PCBs deleted since the last look

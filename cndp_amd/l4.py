@@ -26,6 +26,13 @@ against the connections' TCB snapshots, kept in a TcbTable beside the TCP table:
     tcbs.set(1, state=N.CNDP_TCPS_ESTABLISHED, rcv_nxt=..., snd_una=..., ...)
     s = c.tcp_segment(frames, out, tcbs, t, now=ticks)       # opt, verdict, stats
 
+The transmit side of those connections (include/cndp_tcpout.h): per-TCB transmit
+attributes and, on the calling thread, the rule that builds options, header and
+payload in front of ip4_output's CNDP_TX_IP4 mode:
+
+    tcbs.tx_set(1, tflags=N.CNDP_TCBF_REQ_TSTAMP | N.CNDP_TCBF_RCVD_TSTAMP, rcv_scale=7)
+    o = tcbs.output_host(slab, n, pcb, now=ticks, txseg=descs, snd=sendbuf, src_off=offs, stride=2048, data_off=64)
+
 Addresses and ports are kept in network order, as the u32 / u16 a
 little-endian host loads from the frame; add() and lookup keys take host
 integers or dotted quads and convert.
@@ -167,6 +174,10 @@ def seg_records(seg) -> np.ndarray:
 # ---------------------------------------------------------------------------
 # struct cndp_tcp_opt
 OPT_DT = np.dtype([("ts_val", "<u4"), ("ts_ecr", "<u4"), ("wnd", "<u4"), ("mss", "<u2"), ("sflags", "<u2")])
+# struct cndp_tcp_txseg
+TXSEG_DT = np.dtype([("seq", "<u4"), ("ack", "<u4"), ("wnd", "<u2"), ("urp", "<u2"), ("len", "<u2"),
+                     ("flags", "u1"), ("rsvd", "u1")])
+TCB_TX_FIELDS = ("tflags", "req_recv_scale", "rcv_scale")
 TCB_FIELDS = ("rcv_nxt", "snd_una", "snd_nxt", "snd_max", "snd_wnd", "snd_cwnd", "ts_recent", "last_ack_sent",
               "rcv_space", "max_mss", "state", "snd_scale", "flags")
 
@@ -225,6 +236,63 @@ class TcbTable:
         N.check(r, "cndp_tcb_get")
         return {k: int(getattr(t, k)) for k in TCB_FIELDS}
 
+    def tx_set_raw(self, idx: int, **fields) -> int:
+        """cndp_tcb_tx_set; returns its result (0 or -errno).  Fields not given are 0."""
+        a = N.TcbTx()
+        for k, v in fields.items():
+            if k not in TCB_TX_FIELDS:
+                raise TypeError(f"struct cndp_tcb_tx has no field {k!r}")
+            setattr(a, k, int(v))
+        return self._L.cndp_tcb_tx_set(self.h, idx, ctypes.byref(a))
+
+    def tx_set(self, idx: int, **fields) -> None:
+        N.check(self.tx_set_raw(idx, **fields), "cndp_tcb_tx_set")
+
+    def tx_get(self, idx: int):
+        """The transmit attributes as a dict, or None when the index has no TCB."""
+        a = N.TcbTx()
+        r = self._L.cndp_tcb_tx_get(self.h, idx, ctypes.byref(a))
+        if r == -2:
+            return None
+        N.check(r, "cndp_tcb_tx_get")
+        return {k: int(getattr(a, k)) for k in TCB_TX_FIELDS}
+
+    def output_host(self, slab: np.ndarray, n: int, pcb, mode: int = N.CNDP_TCPOUT_SEGMENT, now: int = 0,
+                    txseg=None, seg=None, verdict=None, rxmeta=None, sel=None, snd=None, src_off=None,
+                    stride: int = 0, offsets=None, data_off: int = 0, stats=None) -> dict:
+        """cndp_tcp_output_host over host arrays: the stage's rule on the calling
+        thread, writing `slab` (a contiguous uint8 array) in place.  Returns len
+        (uint16), faddr, laddr (uint32), taken (uint8) and stats
+        (uint64[CNDP_TCPOUT_NSTATS], accumulated into `stats` when given)."""
+        assert slab.dtype == np.uint8 and slab.flags["C_CONTIGUOUS"] and slab.flags["WRITEABLE"]
+        m = max(n, 1)
+        out = {"len": np.zeros(m, np.uint16), "faddr": np.zeros(m, np.uint32), "laddr": np.zeros(m, np.uint32),
+               "taken": np.zeros(m, np.uint8),
+               "stats": np.zeros(N.CNDP_TCPOUT_NSTATS, np.uint64) if stats is None else np.array(stats, np.uint64)}
+        keep, given = [], []
+        io = N.TcpOutIo()
+        for name, arr, dt in (("sel", sel, np.uint8), ("pcb", pcb, np.uint32), ("txseg", txseg, TXSEG_DT),
+                              ("seg", seg, SEG_DT), ("verdict", verdict, np.uint8), ("rxmeta", rxmeta, np.uint32),
+                              ("snd", snd, np.uint8), ("src_off", src_off, np.uint64)):
+            if arr is not None:
+                keep.append(_aligned16(arr, dt))
+                given.append((name, keep[-1].copy()))
+                setattr(io, name, keep[-1].ctypes.data)
+        if snd is not None:
+            io.snd_len = int(np.asarray(snd).size)
+        for name in ("len", "faddr", "laddr", "taken", "stats"):
+            setattr(io, name, out[name].ctypes.data)
+        offs = None
+        if offsets is not None:
+            offs = np.ascontiguousarray(offsets, np.uint64)
+        N.check(self._L.cndp_tcp_output_host(self.h, mode, now & 0xFFFFFFFF, slab.ctypes.data, slab.size, stride,
+                                             offs.ctypes.data if offs is not None else None, data_off, n,
+                                             ctypes.byref(io)), "cndp_tcp_output_host")
+        for (name, before), after in zip(given, keep):
+            if not np.array_equal(before, after):
+                raise RuntimeError(f"cndp_tcp_output_host wrote its input {name}")
+        return {k: (v if k == "stats" else v[:n]) for k, v in out.items()}
+
     def segment_host(self, slab: np.ndarray, n: int, rxmeta, pcb, seg, now: int, l4edge=None, sel=None,
                      stride: int = 0, offsets=None, data_off: int = 0, stats=None) -> dict:
         """cndp_tcp_segment_host over host arrays: the stage's rule on the
@@ -250,6 +318,22 @@ class TcbTable:
         N.check(self._L.cndp_tcp_segment_host(self.h, now & 0xFFFFFFFF, ctypes.byref(b), ctypes.byref(io)),
                 "cndp_tcp_segment_host")
         return {"opt": opt[:n], "verdict": verdict[:n], "stats": st}
+
+
+def _aligned16(arr, dt) -> np.ndarray:
+    """A contiguous copy of `arr` as dtype dt whose first byte is 16-byte aligned."""
+    a = np.ascontiguousarray(arr, dt)
+    raw = np.zeros(a.nbytes + 16, np.uint8)
+    o = (-raw.ctypes.data) % 16
+    out = raw[o:o + a.nbytes].view(dt)
+    out[...] = a.reshape(-1)
+    return out
+
+
+def send_optlen(tflags: int, seg_flags: int) -> int:
+    """cndp_tcp_send_optlen: tcp_send_options' length (0, 4, 8, 12, 16 or 20) for a
+    TCB with these CNDP_TCBF_* bits and a segment with these TCP flags."""
+    return int(N.lib().cndp_tcp_send_optlen(tflags & 0xFF, seg_flags & 0xFF))
 
 
 def alloc_tcpseg_outputs(n: int, device) -> dict:

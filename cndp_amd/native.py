@@ -96,6 +96,13 @@ CNDP_SEG_REQ_SCALE = 0x000F
 CNDP_TCPSEG_NSTATS = 8
 CNDP_TCPSEG_VERDICT, CNDP_TCPSEG_TS_UPDATE, CNDP_TCPSEG_FIRST = 0x0F, 0x40, 0x80
 
+# cndp_tcpout.h
+CNDP_TCBF_REQ_SCALE, CNDP_TCBF_RCVD_SCALE, CNDP_TCBF_REQ_TSTAMP, CNDP_TCBF_RCVD_TSTAMP = 0x01, 0x02, 0x04, 0x08
+CNDP_TCPOUT_SEGMENT, CNDP_TCPOUT_RESPOND = 0, 1
+(CNDP_TCPOUT_STAT_SENT, CNDP_TCPOUT_STAT_NOTSEL, CNDP_TCPOUT_STAT_NOPCB, CNDP_TCPOUT_STAT_NOLADDR,
+ CNDP_TCPOUT_STAT_TOOBIG, CNDP_TCPOUT_STAT_RST_IN, CNDP_TCPOUT_STAT_MCAST, CNDP_TCPOUT_STAT_OPTS) = range(8)
+CNDP_TCPOUT_NSTATS = 8
+
 # cndp_fwd.h
 CNDP_FWD_OBJS_MAX = 1 << 24
 CNDP_FWD_NETIFS = 256
@@ -187,6 +194,19 @@ class TcpSegIo(Structure):
     """struct cndp_tcpseg_io (cndp_tcb.h)."""
     _fields_ = [("sel", c_void_p), ("l4edge", c_void_p), ("pcb", c_void_p), ("seg", c_void_p),
                 ("opt", c_void_p), ("verdict", c_void_p), ("stats", c_void_p)]
+
+
+class TcbTx(Structure):
+    """struct cndp_tcb_tx (cndp_tcpout.h)."""
+    _fields_ = [("tflags", c_uint8), ("req_recv_scale", c_uint8), ("rcv_scale", c_uint8), ("rsvd", c_uint8)]
+
+
+class TcpOutIo(Structure):
+    """struct cndp_tcpout_io (cndp_tcpout.h)."""
+    _fields_ = [("sel", c_void_p), ("pcb", c_void_p), ("txseg", c_void_p), ("seg", c_void_p), ("verdict", c_void_p),
+                ("rxmeta", c_void_p), ("snd", c_void_p), ("snd_len", c_uint64), ("src_off", c_void_p),
+                ("len", c_void_p), ("faddr", c_void_p), ("laddr", c_void_p), ("taken", c_void_p),
+                ("stats", c_void_p)]
 
 
 class FwdArp(Structure):
@@ -331,6 +351,12 @@ def lib():
         "cndp_tcb_get": (c_int, [c_void_p, c_uint32, POINTER(Tcb)]),
         "cndp_gpu_tcp_segment": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(TcpSegIo), c_uint32, c_void_p]),
         "cndp_tcp_segment_host": (c_int, [c_void_p, c_uint32, POINTER(Batch), POINTER(TcpSegIo)]),
+        # cndp_tcpout.h
+        "cndp_tcb_tx_set": (c_int, [c_void_p, c_uint32, POINTER(TcbTx)]),
+        "cndp_tcb_tx_get": (c_int, [c_void_p, c_uint32, POINTER(TcbTx)]),
+        "cndp_tcp_output_host": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_uint64, c_uint64, c_void_p,
+                                         c_uint32, c_uint32, POINTER(TcpOutIo)]),
+        "cndp_tcp_send_optlen": (c_uint32, [c_uint8, c_uint8]),
         # cndp_fwd.h
         "cndp_fwd_create": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, POINTER(c_void_p)]),
         "cndp_fwd_free": (None, [c_void_p]),
