@@ -205,6 +205,14 @@ struct KArgs {
     uint32_t rw_parts; // 16-B parts of each rewritten frame written back
 };
 
+// the directory's near image, an argument of k_classify_stream_img alone (KArgs
+// and with it every other kernel stay what they were)
+struct NearArgs {
+    const uint32_t *img; // top[256], then n_mid /8 slots of 256 entries; nullptr: no usable image
+    uint32_t n_mid;
+    uint32_t n_pages;    // KArgs.pages[0 .. n_pages * 256) behind them
+};
+
 #define FAST_THREADS 256
 #define SPEC_CH_K 4 // graph bursts per speculation chunk (SPEC_CH)
 // meta word (spec_meta index) of CNDP_TUNE_SPEC_LISTS:
@@ -890,6 +898,8 @@ __global__ __launch_bounds__(FAST_THREADS) void k_classify_stream(KArgs a, uint6
 // later, a trip ahead of its use (the LDS atomic's return is waited for with
 // the trip's other LDS traffic).
 #define STREAM_BW 8
+#define CNDP_FIB_LDS_DEFAULT 1 /* CNDP_TUNE_FIB_LDS of a new context */
+#define CNDP_FIB_LDS_SD 2      /* the image kernel's store distance in trips */
 template <int MODE, bool NTS, bool LNT>
 __global__ __launch_bounds__(STREAM_BW * 64) void k_classify_stream_bal(KArgs a, uint64_t n_tiles)
 {
@@ -974,6 +984,237 @@ __global__ __launch_bounds__(STREAM_BW * 64) void k_classify_stream_bal(KArgs a,
         }
     }
     // ragged tail (frames past the last whole tile): per-lane path
+    const uint64_t done = n_tiles * 64u;
+    for (uint64_t i = done + (uint64_t)blockIdx.x * NT + tid; i < a.n; i += (uint64_t)gridDim.x * NT) {
+        FastHdr h;
+        fast_load<false>(a, i, h);
+        fast_finish<MODE, false>(a, i, h, s_t, s_reta, s_bins, count);
+    }
+    if (count) {
+        __syncthreads();
+        for (uint32_t k = tid; k < a.n_bins + 2; k += NT)
+            if (s_bins[k])
+                atomicAdd(&a.bins[k], (unsigned long long)s_bins[k]);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_classify_stream_bal for l3fwd with the FIB's first 24 bits in LDS
+// (CNDP_TUNE_FIB_LDS): the block copies the directory's near image -- top[256],
+// the /8 slots in use and the /16 pages in use, at most CNDP_NEAR_CAP_KIB KiB --
+// into LDS behind its first frame loads, and stage A resolves every lane down
+// to the tbl24 entry by up to three dependent LDS reads (lgkmcnt, not the
+// in-order vmcnt queue).  One gather is left, tbl8 behind an extended tbl24
+// entry, issued where the three were (ahead of the frame loads of tile c+2,
+// index 0 when not needed) and consumed with the stores SD trips later:
+//   A  tile c     stage, parse, Toeplitz, LDS walk, the tbl8 gather
+//   D  tile c-SD  queue, bins and the result stores
+// With SD >= 2 the gather is older than frame tile c-SD+2, which trip c-SD+2
+// waited for anyway, so consuming it adds no vmcnt wait of its own.
+// ---------------------------------------------------------------------------
+struct ImgLane { // one lane's packet between stage A and its stores
+    uint32_t et, hs;
+    uint32_t e;   // the tbl24 entry (from LDS); bit 0: extended
+    uint32_t raw; // the tbl8 gather issued for it (consumed SD trips later)
+};
+
+template <bool NTS, bool LNT, int P, int SD>
+__device__ __forceinline__ void stream_trip_img(const KArgs &a, uint64_t n_tiles, uint64_t c, uint64_t cn, uint64_t cd,
+                                                bool dD, uint32_t lane, u32x4 *tile, u32x4 (&r)[2][4],
+                                                ImgLane (&st)[SD], const uint32_t *s_t, const uint16_t *s_reta,
+                                                uint32_t *s_bins, bool count, const uint32_t *s_img,
+                                                uint32_t pg_off)
+{
+    constexpr int MODE = CNDP_MODE_L3FWD;
+    // every load is issued unconditionally, as in stream_trip
+    const uint8_t *base = a.slab + a.data_off;
+    const uint32_t fr_in_k = lane >> 2, part = lane & 3u;
+    // D: tile c-SD -- its tbl8 entry came back long ago
+    const ImgLane od = st[SD - 1];
+    uint32_t nhD = CNDP_NH_INVALID;
+    if (od.et == 0x0800u)
+        nhD = ((od.e & 1u) ? od.raw : od.e) >> 1;
+    // A: tile c -- stage, parse, hash, LDS walk, the tbl8 gather
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        const uint32_t f = 16u * k + fr_in_k;
+        tile[f * 4u + (part ^ ((f >> 2) & 3u))] = r[P][k];
+    }
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t sw = (lane >> 2) & 3u;
+    const u32x4 p0 = tile[lane * 4u + (0u ^ sw)];
+    const u32x4 p1 = tile[lane * 4u + (1u ^ sw)];
+    const u32x4 p2 = tile[lane * 4u + (2u ^ sw)];
+    __builtin_amdgcn_wave_barrier();
+    FastHdr h;
+    const uint64_t i = (c < n_tiles ? c : n_tiles - 1u) * 64u + lane;
+    h.p = base + i * 64u;
+    h.avail = a.slab_len - (a.data_off + i * 64u);
+    h.w3 = p0.w;
+    h.w5 = p1.y;
+    h.w6 = p1.z;
+    h.w7 = p1.w;
+    h.w8 = p2.x;
+    h.w9 = p2.y;
+    const uint32_t et = bswap16(h.w3 & 0xffffu);
+    const uint32_t dst = alignb(h.w8, h.w7, 2);
+    const uint32_t ip = bswap32(dst);
+    ImgLane nb;
+    nb.et = et;
+    // top -> /8 slot -> /16 page, each read taken only behind a set bit 0
+    // (non-IPv4 lanes: no lookup); the indices stay inside the copied image
+    // because the image is consistent: a slot or page id in it is in use
+    uint32_t e = 0;
+    if (et == 0x0800u) {
+        e = s_img[ip >> 24];
+        if (e & 1u)
+            e = s_img[256u + (e >> 1) * 256u + ((ip >> 16) & 0xffu)];
+        if (e & 1u)
+            e = s_img[pg_off + (e >> 1) * 256u + ((ip >> 8) & 0xffu)];
+    }
+    nb.e = e;
+    nb.raw = a.tbl8[(e & 1u) ? (e >> 1) * 256u + (ip & 0xffu) : 0u];
+    nb.hs = 0;
+    bool slow = et == 0x86DDu;
+    if (et == 0x0800u) {
+        const uint32_t ihl = (h.w3 >> 16) & 0xfu;
+        const uint32_t proto = h.w5 >> 24;
+        const uint32_t frag = bswap16(h.w5 & 0xffffu) & 0x3fffu;
+        nb.hs = tz4(s_t, 0, alignb(h.w7, h.w6, 2)) ^ tz4(s_t, 4, dst);
+        if (ihl >= 5 && (proto == 6u || proto == 17u) && frag == 0) {
+            if (ihl == 5)
+                nb.hs ^= tz4(s_t, 8, alignb(h.w9, h.w8, 2));
+            else
+                slow = true;
+        }
+    }
+    if (slow) // IPv6 tuple / IPv4 options: bytes past the staged 48
+        nb.hs = fast_hash<MODE>(a, h, s_t);
+    // frame tile c+2 into the register set just consumed
+    {
+        const u32x4 *g = (const u32x4 *)(base + (cn < n_tiles ? cn : n_tiles - 1u) * 4096u);
+        r[P][0] = ldg4<LNT>((const uint8_t *)(g + lane));
+        r[P][1] = ldg4<LNT>((const uint8_t *)(g + 64 + lane));
+        r[P][2] = ldg4<LNT>((const uint8_t *)(g + 128 + lane));
+        r[P][3] = ldg4<LNT>((const uint8_t *)(g + 192 + lane));
+    }
+    // D: the stores of tile c-SD
+    if (dD)
+        fast_emit<MODE, NTS>(a, cd * 64u + lane, od.et, nhD, od.hs, s_reta, s_bins, count);
+#pragma unroll
+    for (int k = SD - 1; k > 0; k--)
+        st[k] = st[k - 1];
+    st[0] = nb;
+}
+
+// Host side at the end of this file: the template's first use decides where its
+// instantiations land in the code object, and behind every other kernel they
+// leave those at the addresses they had (C2's kernel measured 0.5 % slower with
+// these two in front of it, same instructions).
+static int stream_img_init(void);
+static void stream_img_launch(bool nts, uint32_t blocks, uint32_t lds, hipStream_t s, const KArgs &a,
+                              uint64_t n_tiles, const NearArgs &nr);
+
+extern __shared__ __attribute__((aligned(16))) uint32_t s_near_img[]; // (1 + n_mid + n_pages) KiB
+
+template <bool NTS, bool LNT, int SD>
+__global__ __launch_bounds__(STREAM_BW * 64) void k_classify_stream_img(KArgs a, uint64_t n_tiles, NearArgs nr)
+{
+    __shared__ uint32_t s_t[TAB4_POS * 256];
+    __shared__ uint16_t s_reta[CNDP_RETA_MAX];
+    __shared__ uint32_t s_bins[CNDP_BINS_MAX + 2];
+    __shared__ __attribute__((aligned(16))) u32x4 s_tile[STREAM_BW][256];
+    __shared__ uint32_t s_next;
+    constexpr uint32_t NT = STREAM_BW * 64;
+    constexpr int MODE = CNDP_MODE_L3FWD;
+
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = tid; k < TAB4_POS * 256; k += NT)
+        s_t[k] = a.ttab[k];
+    for (uint32_t k = tid; k <= a.reta_mask; k += NT)
+        s_reta[k] = a.reta[k];
+    const bool count = a.bins != nullptr;
+    if (count)
+        for (uint32_t k = tid; k < a.n_bins + 2; k += NT)
+            s_bins[k] = 0;
+    if (tid == 0)
+        s_next = 3u * STREAM_BW;
+    const uint32_t lane = tid & 63u, wv = tid >> 6;
+    u32x4 *tile = s_tile[wv];
+    const uint8_t *base = a.slab + a.data_off;
+    const uint64_t G = gridDim.x, b = blockIdx.x;
+    const uint64_t NONE = ~0ull;
+    const uint64_t nk = b < n_tiles ? (n_tiles - b + G - 1) / G : 0;
+    auto tile_of = [&](uint64_t k) { return k < nk ? b + k * G : NONE; };
+    // the wave's first three tiles, static; two of them loaded now
+    uint64_t q0 = tile_of(wv), q1 = tile_of(wv + STREAM_BW), q2 = tile_of(wv + 2u * STREAM_BW);
+    u32x4 r[2][4];
+#pragma unroll
+    for (uint32_t s = 0; s < 2; s++) {
+        const uint64_t ts = s ? q1 : q0;
+        const u32x4 *g = (const u32x4 *)(base + (ts < n_tiles ? ts : n_tiles - 1u) * 4096u);
+        r[s][0] = ldg4<LNT>((const uint8_t *)(g + lane));
+        r[s][1] = ldg4<LNT>((const uint8_t *)(g + 64 + lane));
+        r[s][2] = ldg4<LNT>((const uint8_t *)(g + 128 + lane));
+        r[s][3] = ldg4<LNT>((const uint8_t *)(g + 192 + lane));
+    }
+    // the near image behind the first frame loads: coalesced 16-B copies of L2 hits
+    {
+        const uint32_t n4a = 64u * (1u + nr.n_mid), n4b = 64u * nr.n_pages;
+        u32x4 *d = (u32x4 *)s_near_img;
+        const u32x4 *sa = (const u32x4 *)nr.img, *sp = (const u32x4 *)a.pages;
+        for (uint32_t k = tid; k < n4a; k += NT)
+            d[k] = sa[k];
+        for (uint32_t k = tid; k < n4b; k += NT)
+            d[n4a + k] = sp[k];
+    }
+    __syncthreads();
+    auto draw = [&](uint64_t prev) -> uint32_t {
+        uint32_t v = 0;
+        if (prev != NONE && lane == 0)
+            v = atomicAdd(&s_next, 1u);
+        return v;
+    };
+    uint32_t kv = draw(q2);
+    const uint32_t pg_off = 256u + nr.n_mid * 256u; // the /16 pages behind top and the /8 slots
+    uint64_t hs[SD]; // the tiles in flight behind stage A; hs[SD - 1] is stage D's
+    ImgLane st[SD];
+#pragma unroll
+    for (int k = 0; k < SD; k++) {
+        hs[k] = NONE;
+        st[k] = ImgLane{0, 0, 0, 0};
+    }
+    auto idle = [&]() {
+        bool z = q0 == NONE;
+#pragma unroll
+        for (int k = 0; k < SD; k++)
+            z = z && hs[k] == NONE;
+        return z; // wave-uniform
+    };
+    auto advance = [&]() {
+        const uint64_t qn = q2 == NONE ? NONE : tile_of(__builtin_amdgcn_readfirstlane(kv));
+        kv = draw(qn);
+#pragma unroll
+        for (int k = SD - 1; k > 0; k--)
+            hs[k] = hs[k - 1];
+        hs[0] = q0;
+        q0 = q1;
+        q1 = q2;
+        q2 = qn;
+    };
+    for (;;) {
+        if (idle())
+            break;
+        stream_trip_img<NTS, LNT, 0, SD>(a, n_tiles, q0, q2, hs[SD - 1], hs[SD - 1] != NONE, lane, tile, r, st, s_t,
+                                         s_reta, s_bins, count, s_near_img, pg_off);
+        advance();
+        if (idle())
+            break;
+        stream_trip_img<NTS, LNT, 1, SD>(a, n_tiles, q0, q2, hs[SD - 1], hs[SD - 1] != NONE, lane, tile, r, st, s_t,
+                                         s_reta, s_bins, count, s_near_img, pg_off);
+        advance();
+    }
+    // ragged tail (frames past the last whole tile): per-lane path, global tables
     const uint64_t done = n_tiles * 64u;
     for (uint64_t i = done + (uint64_t)blockIdx.x * NT + tid; i < a.n; i += (uint64_t)gridDim.x * NT) {
         FastHdr h;
@@ -4421,6 +4662,9 @@ struct cndp_gpu_ctx {
     int tune_bpc;         // CNDP_TUNE_BLOCKS_PER_CU
     int tune_tile;        // CNDP_TUNE_TILE
     int tune_dir16;       // CNDP_TUNE_DIR16
+    int tune_fib_lds;     // CNDP_TUNE_FIB_LDS: 0 off, 1 on where the image fits
+    int fib_lds_ok;       // the image kernels may take their LDS (hipFuncSetAttribute succeeded)
+    uint64_t n_fib_lds;   // CNDP_STAT_FIB_LDS: classify launches that took the LDS-image kernel
     int tune_cnet_tile;   // CNDP_TUNE_CNET_TILE
     int tune_lnt;         // CNDP_TUNE_LOAD_NT
     int tune_spec_scan;   // CNDP_TUNE_SPEC_SCAN
@@ -4607,6 +4851,13 @@ extern "C" int cndp_gpu_init(int device, cndp_gpu_ctx_t **out)
     c->tune_bpc = 0; // auto: 2 for the streamed tile kernel, 4 otherwise
     c->tune_tile = 1;
     c->tune_dir16 = 1;
+    {
+        // CNDP_TUNE_FIB_LDS in the environment: the context's default (A/B through unchanged callers)
+        const char *fe = getenv("CNDP_TUNE_FIB_LDS");
+        const int fv = fe ? atoi(fe) : CNDP_FIB_LDS_DEFAULT;
+        c->tune_fib_lds = fv < 0 || fv > 1 ? CNDP_FIB_LDS_DEFAULT : fv;
+        c->fib_lds_ok = stream_img_init();
+    }
     c->tune_cnet_tile = 1;
     c->tune_lnt = 1;
     c->tune_spec_lists = 1;
@@ -4764,6 +5015,8 @@ extern "C" void cndp_tbl_dev_free(struct cndp_tbl *t)
         hipFree(t->dev_dir16);
     if (t->dev_pages)
         hipFree(t->dev_pages);
+    if (t->dev_near)
+        hipFree(t->dev_near);
     if (t->lk_stream)
         hipStreamDestroy((hipStream_t)t->lk_stream);
     if (t->lk_dbuf)
@@ -4776,92 +5029,14 @@ extern "C" void cndp_tbl_dev_free(struct cndp_tbl *t)
     t->dev_old = nullptr;
     t->n_old = t->cap_old = 0;
     hipSetDevice(cur);
-    t->dev_dir16 = t->dev_pages = nullptr;
+    t->dev_dir16 = t->dev_pages = t->dev_near = nullptr;
     t->dev_cap_pages = 0;
     t->dev_tbl24 = t->dev_tbl8 = nullptr;
     t->dev_id = -1;
     t->dev_groups = 0;
 }
 
-// ---- /16 directory maintenance (host) ---------------------------------------
-static int dir16_page_alloc(struct cndp_tbl *t)
-{
-    if (t->n_free)
-        return (int)t->page_free[--t->n_free];
-    if (t->page_hwm == t->cap_pages) {
-        const uint32_t ncap = t->cap_pages ? t->cap_pages * 2 : 64;
-        uint32_t *np = (uint32_t *)realloc(t->pages, (size_t)ncap * 256 * 4);
-        uint32_t *nf = (uint32_t *)realloc(t->page_free, (size_t)ncap * 4);
-        if (!np || !nf) {
-            if (np)
-                t->pages = np;
-            if (nf)
-                t->page_free = nf;
-            return -ENOMEM;
-        }
-        t->pages = np;
-        t->page_free = nf;
-        t->cap_pages = ncap;
-    }
-    return (int)t->page_hwm++;
-}
-
-// refresh the directory entries of /16 blocks [k0, k1]
-static int dir16_update(struct cndp_tbl *t, uint32_t k0, uint32_t k1)
-{
-    if (!t->dir16) {
-        t->dir16 = (uint32_t *)calloc(65536, 4);
-        t->page_of = (int32_t *)malloc(65536 * 4);
-        if (!t->dir16 || !t->page_of)
-            return -ENOMEM;
-        for (uint32_t k = 0; k < 65536; k++)
-            t->page_of[k] = -1;
-        k0 = 0;
-        k1 = 65535;
-        t->dd_lo = t->dp_lo = ~0ULL;
-        t->dd_hi = t->dp_hi = 0;
-    }
-    const uint32_t *t24 = (const uint32_t *)t->tbl24;
-    for (uint32_t k = k0; k <= k1; k++) {
-        const uint32_t *e = t24 + (size_t)k * 256;
-        const uint32_t v = e[0];
-        bool uni = !(v & 1u);
-        for (uint32_t b = 1; uni && b < 256; b++)
-            uni = e[b] == v;
-        uint32_t nd;
-        if (uni) {
-            if (t->page_of[k] >= 0) {
-                t->page_free[t->n_free++] = (uint32_t)t->page_of[k];
-                t->page_of[k] = -1;
-                t->n_pages_used--;
-            }
-            nd = v;
-        } else {
-            if (t->page_of[k] < 0) {
-                const int pg = dir16_page_alloc(t);
-                if (pg < 0)
-                    return pg;
-                t->page_of[k] = pg;
-                t->n_pages_used++;
-            }
-            const uint64_t pe = (uint64_t)t->page_of[k] * 256;
-            memcpy(t->pages + pe, e, 256 * 4);
-            if (pe < t->dp_lo)
-                t->dp_lo = pe;
-            if (pe + 256 > t->dp_hi)
-                t->dp_hi = pe + 256;
-            nd = ((uint32_t)t->page_of[k] << 1) | 1u;
-        }
-        if (t->dir16[k] != nd || t->dd_hi == 0) {
-            t->dir16[k] = nd;
-            if (k < t->dd_lo)
-                t->dd_lo = k;
-            if ((uint64_t)k + 1 > t->dd_hi)
-                t->dd_hi = (uint64_t)k + 1;
-        }
-    }
-    return 0;
-}
+// ---- /16 directory maintenance (host): fib_near.c ----------------------------
 
 // Device buffers replaced by a sync (caller holds dev_lock): a launch that
 // took an address under dev_lock (tbl_acquire) may still be on its way, so a
@@ -4905,7 +5080,7 @@ static int dir16_sync(struct cndp_tbl *t, hipStream_t s, const struct cndp_range
     for (uint32_t k = 0; k < nr || (!t->dir16 && k == 0); k++) {
         const uint64_t lo = k < nr ? rg[k].lo : 0, hi = k < nr ? rg[k].hi : 0;
         if (hi > lo || !t->dir16) {
-            int r = dir16_update(t, (uint32_t)(lo >> 8), (uint32_t)((hi ? hi - 1 : 0) >> 8));
+            int r = cndp_tbl_dir16_update(t, (uint32_t)(lo >> 8), (uint32_t)((hi ? hi - 1 : 0) >> 8));
             if (r)
                 return r;
         }
@@ -4934,6 +5109,38 @@ static int dir16_sync(struct cndp_tbl *t, hipStream_t s, const struct cndp_range
                                (t->dp_hi - t->dp_lo) * 4, hipMemcpyHostToDevice, s));
     t->dd_lo = t->dp_lo = ~0ULL;
     t->dd_hi = t->dp_hi = 0;
+    return 0;
+}
+
+// The near image goes up only with the sync of a launch that will read it
+// (near set: the l3fwd classify), not with every sync: a sync behind scattered
+// route changes -- a host lookup's -- would pay one more copy for an image it
+// never reads (measured: 63 against 51 us for 8 changes, 117 against 77 for
+// 64).  Until then the directory refresh only marks the /8 blocks it touched;
+// the caller refreshes the host image first, whose dirty range this uploads.
+// Top and all 256 /8 slots are one fixed buffer, cleared when allocated like
+// the host's, so what was never dirty is 0 on both sides.  It is overwritten
+// in place on the caller's stream, as tbl24, tbl8 and dir16 are: a launch
+// still running on another stream while routes change reads a mix of old and
+// new entries from any of them (the mirror's contract).
+// *copied: the caller waits for the stream before the host image may change.
+static int near_upload(struct cndp_tbl *t, hipStream_t s, bool *copied)
+{
+    if (!t->near_img)
+        return 0;
+    if (!t->dev_near) {
+        HIP_TRY(hipMalloc(&t->dev_near, (size_t)CNDP_NEAR_ENT * 4));
+        HIP_TRY(hipMemsetAsync(t->dev_near, 0, (size_t)CNDP_NEAR_ENT * 4, s));
+        t->dn_lo = 0;
+        t->dn_hi = 256u + (uint64_t)t->mid_hwm * 256u;
+    }
+    if (t->dn_hi > t->dn_lo) {
+        HIP_TRY(hipMemcpyAsync((uint32_t *)t->dev_near + t->dn_lo, t->near_img + t->dn_lo,
+                               (t->dn_hi - t->dn_lo) * 4, hipMemcpyHostToDevice, s));
+        *copied = true;
+    }
+    t->dn_lo = ~0ULL;
+    t->dn_hi = 0;
     return 0;
 }
 
@@ -5102,7 +5309,8 @@ static int tbl_dev_paint(struct cndp_tbl *t, hipStream_t s, bool paint24, bool p
 }
 
 // caller holds t->dev_lock
-static int tbl_dev_sync_locked(struct cndp_tbl *t, void *stream)
+// near: the caller's launch may read the near image (refreshed and uploaded here too)
+static int tbl_dev_sync_locked(struct cndp_tbl *t, void *stream, bool near = false)
 {
     if (!t || !t->tbl24)
         return -EINVAL;
@@ -5176,9 +5384,17 @@ static int tbl_dev_sync_locked(struct cndp_tbl *t, void *stream)
         if (r)
             return r;
     }
+    bool near_up = false;
+    if (near && has_dir16) {
+        int r = cndp_tbl_near_refresh(t);
+        if (!r && cndp_tbl_near_fits(t))
+            r = near_upload(t, s, &near_up);
+        if (r)
+            return r;
+    }
     // the host image (and the painter's staging) may change right after we
     // return: finish the copies and the paint
-    if (dirty)
+    if (dirty || near_up)
         HIP_TRY(hipStreamSynchronize(s));
     t->d24_lo = t->d8_lo = ~0ULL;
     t->d24_hi = t->d8_hi = 0;
@@ -5208,17 +5424,22 @@ struct TblView {
     const void *t24, *t8;
     uint32_t nh_sz;
     const uint32_t *d16, *pages; // the /16 directory (4-B DIR-24-8 images), or null
+    const uint32_t *near;        // its near image when it fits the LDS cap (else null):
+    uint32_t n_mid, page_hwm;    // top, n_mid /8 slots; pages[0 .. page_hwm) behind them
 };
 static inline TblView tbl_view(const struct cndp_tbl *t)
 {
     const bool dir = t->dev_dir16 && t->dev_pages;
+    // (the device copy is current only when near_upload left nothing dirty)
+    const bool near = dir && t->dev_near && t->dn_hi <= t->dn_lo && cndp_tbl_near_fits(t);
     return TblView{t->dev_tbl24, t->dev_tbl8, t->nh_sz, dir ? (const uint32_t *)t->dev_dir16 : nullptr,
-                   dir ? (const uint32_t *)t->dev_pages : nullptr};
+                   dir ? (const uint32_t *)t->dev_pages : nullptr, near ? (const uint32_t *)t->dev_near : nullptr,
+                   near ? t->mid_hwm : 0u, near ? t->page_hwm : 0u};
 }
-static int tbl_acquire(struct cndp_tbl *t, hipStream_t s, TblView *v)
+static int tbl_acquire(struct cndp_tbl *t, hipStream_t s, TblView *v, bool near = false)
 {
     pthread_mutex_lock(&t->dev_lock);
-    const int r = tbl_dev_sync_locked(t, s);
+    const int r = tbl_dev_sync_locked(t, s, near);
     if (!r) {
         *v = tbl_view(t);
         __atomic_add_fetch(&t->views, 1u, __ATOMIC_RELAXED);
@@ -5576,8 +5797,8 @@ static int spec_scratch(cndp_gpu_ctx_t *c, uint64_t n, uint64_t nb)
 }
 
 static int classify_cnet(cndp_gpu_ctx_t *c, const struct cndp_batch *b, KArgs &a, hipStream_t s);
-static int classify_l3(cndp_gpu_ctx_t *c, const struct cndp_batch *b, KArgs &a, hipStream_t s, uint16_t *rw_tx,
-                       bool *fused);
+static int classify_l3(cndp_gpu_ctx_t *c, const struct cndp_batch *b, KArgs &a, const NearArgs &nr, hipStream_t s,
+                       uint16_t *rw_tx, bool *fused);
 
 static int classify_launch(cndp_gpu_ctx_t *c, const struct cndp_batch *b, void *stream, uint16_t *rw_tx,
                            bool *fused, const TblView *v4, const TblView *v6);
@@ -5597,7 +5818,8 @@ static int classify_impl(cndp_gpu_ctx_t *c, const struct cndp_batch *b, void *st
     struct cndp_tbl *t4 = b->mode != CNDP_MODE_HASH ? &c->fib4->t : nullptr;
     struct cndp_tbl *t6 = b->mode == CNDP_MODE_CNET ? &c->fib6->t : nullptr;
     TblView v4{}, v6{};
-    if (t4 && (r = tbl_acquire(t4, (hipStream_t)stream, &v4)))
+    const bool near = b->mode == CNDP_MODE_L3FWD && c->tune_fib_lds && c->fib_lds_ok && c->tune_dir16;
+    if (t4 && (r = tbl_acquire(t4, (hipStream_t)stream, &v4, near)))
         return r;
     if (t6 && (r = tbl_acquire(t6, (hipStream_t)stream, &v6))) {
         tbl_release(t4);
@@ -5617,6 +5839,7 @@ static int classify_launch(cndp_gpu_ctx_t *c, const struct cndp_batch *b, void *
     int r;
     KArgs a;
     memset(&a, 0, sizeof(a));
+    NearArgs nr{nullptr, 0, 0};
     a.slab = (const uint8_t *)b->slab;
     a.slab_len = b->slab_len;
     a.stride = b->stride;
@@ -5631,6 +5854,8 @@ static int classify_launch(cndp_gpu_ctx_t *c, const struct cndp_batch *b, void *
         if (c->tune_dir16 && v4->d16) {
             a.dir16 = v4->d16;
             a.pages = v4->pages;
+            if (v4->near)
+                nr = NearArgs{v4->near, v4->n_mid, v4->page_hwm};
         }
     }
     if (v6) {
@@ -5657,7 +5882,7 @@ static int classify_launch(cndp_gpu_ctx_t *c, const struct cndp_batch *b, void *
         const int r2 = scratch_release(c, s);
         return r ? r : r2;
     }
-    return classify_l3(c, b, a, s, rw_tx, fused);
+    return classify_l3(c, b, a, nr, s, rw_tx, fused);
 }
 
 static int classify_cnet(cndp_gpu_ctx_t *c, const struct cndp_batch *b, KArgs &a, hipStream_t s)
@@ -5835,8 +6060,8 @@ static int classify_cnet(cndp_gpu_ctx_t *c, const struct cndp_batch *b, KArgs &a
     return 0;
 }
 
-static int classify_l3(cndp_gpu_ctx_t *c, const struct cndp_batch *b, KArgs &a, hipStream_t s, uint16_t *rw_tx,
-                       bool *fused)
+static int classify_l3(cndp_gpu_ctx_t *c, const struct cndp_batch *b, KArgs &a, const NearArgs &nr, hipStream_t s,
+                       uint16_t *rw_tx, bool *fused)
 {
     {
         uint32_t g = blocks_for(b->n, FAST_THREADS);
@@ -5871,6 +6096,18 @@ static int classify_l3(cndp_gpu_ctx_t *c, const struct cndp_batch *b, KArgs &a, 
                 *fused = true;
                 hipLaunchKernelGGL(rfns[nti][li], dim3(gt), dim3(FAST_THREADS), 0, s, a, n_tiles);
                 HIP_TRY(hipGetLastError());
+                return 0;
+            }
+            if (c->tune_stream_bal != 1 && c->tune_fib_lds && c->fib_lds_ok && li && nr.img &&
+                b->mode == CNDP_MODE_L3FWD) {
+                // the same schedule with the FIB's first 24 bits in LDS: [nt stores]
+                const uint32_t lds = (1u + nr.n_mid + nr.n_pages) * 1024u;
+                uint32_t gb = (uint32_t)c->num_cu * (c->tune_bpc ? (uint32_t)c->tune_bpc : 1u);
+                if ((uint64_t)gb > n_tiles)
+                    gb = (uint32_t)n_tiles;
+                stream_img_launch(nti != 0, gb, lds, s, a, n_tiles, nr);
+                HIP_TRY(hipGetLastError());
+                __atomic_add_fetch(&c->n_fib_lds, 1u, __ATOMIC_RELAXED);
                 return 0;
             }
             if (c->tune_stream_bal != 1) {
@@ -8395,6 +8632,8 @@ extern "C" int cndp_gpu_mq_wait(cndp_gpu_mq_t *q)
 
 extern "C" int64_t cndp_gpu_get_stat(cndp_gpu_ctx_t *c, int key)
 {
+    if (c && key == CNDP_STAT_FIB_LDS)
+        return (int64_t)__atomic_load_n(&c->n_fib_lds, __ATOMIC_RELAXED);
     if (!c || (key != CNDP_STAT_CNET_WORKLIST && key != CNDP_STAT_CNET_UNIFORM && key != CNDP_STAT_SPEC_ERR))
         return -EINVAL;
     if (!c->sp_hint)
@@ -8485,6 +8724,11 @@ extern "C" int cndp_gpu_set_tuning(cndp_gpu_ctx_t *c, int key, int value)
     case CNDP_TUNE_HOST_WINDOW:
         c->tune_host_window = value ? 1 : 0;
         return 0;
+    case CNDP_TUNE_FIB_LDS:
+        if (value < 0 || value > 1)
+            return -EINVAL;
+        c->tune_fib_lds = value;
+        return 0;
     case CNDP_TUNE_SPEC_WAIT:
         if (value == 0 || value < -1 || value > 40000000)
             return -EINVAL;
@@ -8523,3 +8767,27 @@ extern "C" int cndp_gpu_debug_spec_stamps(unsigned long long *out, uint32_t n)
 #endif
 
 extern "C" const char *cndp_gpu_version(void) { return CNDP_VERSION; }
+
+// ---- k_classify_stream_img, host side (last: see the declarations above it) --
+typedef void (*stream_img_fn)(KArgs, uint64_t, NearArgs);
+static const stream_img_fn stream_img_fns[2] = {k_classify_stream_img<false, true, CNDP_FIB_LDS_SD>,
+                                                k_classify_stream_img<true, true, CNDP_FIB_LDS_SD>};
+
+// static (49 KiB) + image LDS pass the 64 KiB a kernel gets by default; returns
+// 0 where the device refuses (the context then keeps to the gathering kernel)
+static int stream_img_init(void)
+{
+    int ok = 1;
+    for (int k = 0; k < 2; k++)
+        if (hipFuncSetAttribute((const void *)stream_img_fns[k], hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(CNDP_NEAR_CAP_KIB * 1024u)) != hipSuccess)
+            ok = 0;
+    (void)hipGetLastError();
+    return ok;
+}
+
+static void stream_img_launch(bool nts, uint32_t blocks, uint32_t lds, hipStream_t s, const KArgs &a,
+                              uint64_t n_tiles, const NearArgs &nr)
+{
+    hipLaunchKernelGGL(stream_img_fns[nts ? 1 : 0], dim3(blocks), dim3(STREAM_BW * 64), lds, s, a, n_tiles, nr);
+}

@@ -157,6 +157,7 @@ static void tbl_fini(struct cndp_tbl *t)
     free(t->page_of);
     free(t->pages);
     free(t->page_free);
+    free(t->near_img);
     pthread_mutex_destroy(&t->dev_lock);
     memset(t, 0, sizeof(*t));
 }

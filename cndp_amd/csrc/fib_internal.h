@@ -73,6 +73,22 @@ struct cndp_tbl {
     void *dev_dir16;
     void *dev_pages;
     uint32_t dev_cap_pages;
+    /* "near image" of the directory (fib_near.c), small enough for a kernel to
+     * copy into LDS: a lossless re-encoding of dir16 as
+     *   near_img[a], a = ip >> 24      the dir16 value shared by all 256 /16 blocks
+     *                              of /8 a (bit0 clear), or (slot << 1) | 1
+     *   near_img[256 + slot*256 + b]   a verbatim copy of dir16[a*256 + b]
+     * in one buffer of CNDP_NEAR_ENT entries (top, then 256 mid slots); with
+     * pages[0 .. page_hwm) behind it a lookup walks top -> mid -> page -> tbl8.
+     * A directory refresh only marks the /8 blocks it touched (near_stale); the
+     * image catches up when someone wants it (cndp_tbl_near_refresh). */
+    uint32_t *near_img;
+    int16_t mid_of[256];   /* mid slot per /8, -1 = uniform */
+    uint8_t mid_free[256]; /* freed slots (a stack) */
+    uint32_t n_mid_free, n_mid_used, mid_hwm;
+    uint64_t near_stale[4]; /* /8 blocks whose dir16 entries were refreshed since the image was */
+    uint64_t dn_lo, dn_hi; /* dirty near entries */
+    void *dev_near;        /* CNDP_NEAR_ENT entries */
     /* host-array lookups (cne_fib_lookup_bulk): callers are many forwarding
      * threads on one FIB (examples/cndpfwd/l3-fwd.c:85).  dev_lock guards the
      * host image, its dirty ranges and the device mirror; each small call
@@ -117,6 +133,25 @@ struct cne_fib6 {
     struct cndp_rib rib;
     struct cndp_tbl t;
 };
+
+/* fib_near.c: host maintenance of the /16 directory and its near image (plain
+ * C, no device call; the caller holds dev_lock) */
+#define CNDP_NEAR_ENT (257u * 256u)
+#define CNDP_NEAR_CAP_KIB 32u /* an image of at most this many 1-KiB pages is usable from LDS */
+int cndp_tbl_dir16_update(struct cndp_tbl *t, uint32_t k0, uint32_t k1);
+int cndp_tbl_dir16_refresh(struct cndp_tbl *t);
+static inline uint32_t cndp_tbl_near_kib(const struct cndp_tbl *t)
+{
+    return 1u + t->mid_hwm + t->page_hwm;
+}
+int cndp_tbl_near_refresh(struct cndp_tbl *t);
+/* the image is up to the directory and small enough */
+static inline int cndp_tbl_near_fits(const struct cndp_tbl *t)
+{
+    return t->near_img && !(t->near_stale[0] | t->near_stale[1] | t->near_stale[2] | t->near_stale[3]) &&
+           cndp_tbl_near_kib(t) <= CNDP_NEAR_CAP_KIB;
+}
+uint32_t cndp_tbl_near_lookup(const struct cndp_tbl *t, uint32_t ip);
 
 /* implemented in cndp_gpu.hip (device side of the mirror) */
 int cndp_tbl_dev_sync(struct cndp_tbl *t, void *stream);

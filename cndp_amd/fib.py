@@ -97,6 +97,22 @@ class Fib:
         t8 = np.ctypeslib.as_array((ctypes.c_uint8 * (im.tbl8_groups * 256 * esz)).from_address(im.tbl8))
         return t24.view(dt), t8.view(dt)
 
+    def near_info(self) -> dict:
+        """The near image (cndp_fib_near_info) after a refresh: its size in KiB, the cap,
+        whether it fits, and the /8 and /16 pages in use / ever allocated."""
+        N.check(self._L.cndp_fib_near_refresh(self.h), "cndp_fib_near_refresh")
+        im = N.FibNearInfo()
+        N.check(self._L.cndp_fib_near_info(self.h, ctypes.byref(im)), "cndp_fib_near_info")
+        return {k: getattr(im, k) for k, _ in N.FibNearInfo._fields_}
+
+    def near_lookup(self, ips) -> np.ndarray:
+        """cndp_fib_near_lookup: the host walk of the near image (the LDS kernel's rule)."""
+        ips = np.ascontiguousarray(ips, dtype=np.uint32)
+        out = np.zeros(len(ips), dtype=np.uint64)
+        N.check(self._L.cndp_fib_near_lookup(self.h, ips.ctypes.data, out.ctypes.data, len(ips)),
+                "cndp_fib_near_lookup")
+        return out
+
     def stats(self):
         r, u, s = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         N.check(self._L.cndp_fib_stats(self.h, ctypes.byref(r), ctypes.byref(u), ctypes.byref(s)),

@@ -44,12 +44,14 @@ CNDP_TUNE_CNET_SPEC = 9
 CNDP_TUNE_LOAD_NT = 10
 CNDP_TUNE_SPEC_SCAN = 11
 CNDP_STAT_CNET_WORKLIST, CNDP_STAT_CNET_UNIFORM, CNDP_STAT_SPEC_ERR = 1, 2, 3
+CNDP_STAT_FIB_LDS = 4
 CNDP_TUNE_MBUF_HASH = 12
 CNDP_TUNE_CNET_FOLD = 13
 CNDP_TUNE_SPEC_GRID = 14
 CNDP_TUNE_SPEC_LISTS = 15
 CNDP_TUNE_SPEC_TYPES = 16
 CNDP_TUNE_STREAM_BAL = 17
+CNDP_TUNE_FIB_LDS = 20
 CNDP_TUNE_SPEC_WAIT = 18
 CNDP_TUNE_HOST_WINDOW = 19
 CNDP_MQ_IP4_LOOKUP, CNDP_MQ_CNET, CNDP_MQ_MAC_SWAP, CNDP_MQ_IP4_REWRITE = 0, 1, 2, 3
@@ -145,6 +147,12 @@ class FibConf(Structure):
 class FibImage(Structure):
     _fields_ = [("nh_sz", c_uint32), ("tbl8_groups", c_uint32), ("tbl24", c_void_p),
                 ("tbl8", c_void_p), ("def_nh", c_uint64)]
+
+
+class FibNearInfo(Structure):
+    """struct cndp_fib_near_info (cndp_fib.h)."""
+    _fields_ = [("kib", c_uint32), ("cap_kib", c_uint32), ("fits", c_uint32), ("mid_used", c_uint32),
+                ("mid_hwm", c_uint32), ("pages_used", c_uint32), ("page_hwm", c_uint32)]
 
 
 class Batch(Structure):
@@ -282,6 +290,9 @@ def lib():
         "cndp_fib6_stats": (c_int, [c_void_p, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]),
         "cndp_fib_sync_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
         "cndp_fib6_sync_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+        "cndp_fib_near_refresh": (c_int, [c_void_p]),
+        "cndp_fib_near_info": (c_int, [c_void_p, POINTER(FibNearInfo)]),
+        "cndp_fib_near_lookup": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
         # cndp_node.h
         "cne_node_ip4_route_add": (c_int, [c_uint32, c_uint8, c_uint16, c_int]),
         "cne_node_ip4_rewrite_add": (c_int, [c_uint16, c_void_p, c_uint8, c_uint16]),

@@ -190,6 +190,24 @@ int cndp_fib6_stats(struct cne_fib6 *fib, uint32_t *routes, uint32_t *tbl8_used,
 int cndp_fib_sync_stats(struct cne_fib *fib, uint64_t *bytes, uint64_t *cmds);
 int cndp_fib6_sync_stats(struct cne_fib6 *fib, uint64_t *bytes, uint64_t *cmds);
 
+/* The "near image" of a 4-B DIR-24-8 FIB: its first 24 bits as 1-KiB pages
+ * (one indexed by ip >> 24, one per /8 that is not uniform, one per /16 that
+ * is not uniform), which the l3fwd classify kernel copies into LDS when they
+ * are at most cap_kib (CNDP_TUNE_FIB_LDS).  Host side only, no device call:
+ * _refresh brings it up to the routes added and deleted so far (the classify
+ * call does before a launch that reads it), _info reports its size as of the
+ * last refresh (-ENOENT before the first; fits is 0 while it is behind), _lookup
+ * refreshes and walks it by the kernel's rule (top -> /8 page -> /16 page ->
+ * tbl8); the results equal cne_fib_lookup_bulk's. */
+struct cndp_fib_near_info {
+    uint32_t kib, cap_kib, fits; /* 1 + mid_hwm + page_hwm; the cap; kib <= cap_kib */
+    uint32_t mid_used, mid_hwm;  /* /8 pages in use / ever allocated (freed ones are reused) */
+    uint32_t pages_used, page_hwm;
+};
+int cndp_fib_near_refresh(struct cne_fib *fib);
+int cndp_fib_near_info(struct cne_fib *fib, struct cndp_fib_near_info *out);
+int cndp_fib_near_lookup(struct cne_fib *fib, const uint32_t *ips, uint64_t *next_hops, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

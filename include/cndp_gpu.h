@@ -459,7 +459,16 @@ int cndp_gpu_bin_ids(cndp_gpu_ctx_t *ctx, uint32_t mode, const uint32_t *nh, con
  *                           wider than 64 B (the AF_XDP UMEM layout): 1 = only each frame's
  *                           first 64 bytes from data_off cross PCIe, one strided 2-D copy per
  *                           chunk into packed 64-B slots (the parse reads no byte past them;
- *                           default), 0 = the whole slab is mirrored */
+ *                           default), 0 = the whole slab is mirrored
+ *   CNDP_TUNE_FIB_LDS       l3fwd classify of packed 64-B slots on the balanced schedule
+ *                           (CNDP_TUNE_STREAM_BAL 0 / 2, CNDP_TUNE_LOAD_NT 1, CNDP_TUNE_DIR16 1):
+ *                           1 = when the FIB's near image (cndp_fib.h: the /8, /16 and
+ *                           tbl24 levels as 1-KiB pages) is at most 32 KiB the block
+ *                           copies it into LDS and only the tbl8 level is gathered from
+ *                           memory; a larger image, or a device that refuses the kernel
+ *                           its LDS, takes the gathering kernel.  0 = always the gathering
+ *                           kernel.  A new context takes its value from the environment
+ *                           variable of the same name when set */
 #define CNDP_TUNE_NT 1
 #define CNDP_TUNE_UNROLL 2
 #define CNDP_TUNE_BLOCKS_PER_CU 3
@@ -479,6 +488,7 @@ int cndp_gpu_bin_ids(cndp_gpu_ctx_t *ctx, uint32_t mode, const uint32_t *nh, con
 #define CNDP_TUNE_STREAM_BAL 17
 #define CNDP_TUNE_SPEC_WAIT 18
 #define CNDP_TUNE_HOST_WINDOW 19
+#define CNDP_TUNE_FIB_LDS 20
 int cndp_gpu_set_tuning(cndp_gpu_ctx_t *ctx, int key, int value);
 
 /* Observability: the last cnet classify's shape, read from pinned host words
@@ -491,10 +501,13 @@ int cndp_gpu_set_tuning(cndp_gpu_ctx_t *ctx, int key, int value);
  *   CNDP_STAT_CNET_UNIFORM   1 when the last call's ptypes all had the entering
  *                            node state's low byte (the uniform speculation pass)
  *   CNDP_STAT_SPEC_ERR       1 when a speculation pass wait expired and has not been
- *                            reported yet (CNDP_TUNE_SPEC_WAIT) */
+ *                            reported yet (CNDP_TUNE_SPEC_WAIT)
+ *   CNDP_STAT_FIB_LDS        classify launches of this context that ran the LDS-image
+ *                            kernel (CNDP_TUNE_FIB_LDS); with or without speculation */
 #define CNDP_STAT_CNET_WORKLIST 1
 #define CNDP_STAT_CNET_UNIFORM 2
 #define CNDP_STAT_SPEC_ERR 3
+#define CNDP_STAT_FIB_LDS 4
 int64_t cndp_gpu_get_stat(cndp_gpu_ctx_t *ctx, int key);
 
 /* Version / build info string. */
