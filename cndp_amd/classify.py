@@ -264,6 +264,37 @@ class Classifier:
             stream = torch.cuda.current_stream(frames.slab.device).cuda_stream
         N.check(self._L.cndp_gpu_mac_swap(self.h, ctypes.byref(b), stream or None), "cndp_gpu_mac_swap")
 
+    def acl_fwd(self, frames, table, mode: int = N.CNDP_ACL_STRICT, swap: bool = True, in_lport: int = 0,
+                lports=(), n_bins: int | None = None, sel=None, length=None, acl: dict | None = None,
+                stream: int | None = None, slab_len: int | None = None) -> dict:
+        """cndpfwd's ACL mode (cndp_gpu_acl_fwd, include/cndp_acl.h) over every
+        frame (or those with sel[i] != 0): `table` is a built AclTable, `lports`
+        the ports that exist, `in_lport` the one the frames came in on, `length`
+        an optional int16 tensor of data_len.  With `swap` the forwarded frames'
+        MACs are swapped in place.  Returns the stage's outputs as tensors
+        (result, verdict, tx_lport, bin_of, stats; stats accumulates when a
+        previous result is passed back as `acl`)."""
+        import torch
+        from .acl import acl_io, alloc_acl_outputs, default_n_bins
+        dev = frames.slab.device
+        if acl is None:
+            acl = alloc_acl_outputs(frames.n, dev)
+        if n_bins is None:
+            n_bins = default_n_bins(in_lport, lports)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        b = N.Batch()
+        b.n, b.slab = frames.n, frames.slab.data_ptr()
+        b.slab_len = frames.slab.numel() if slab_len is None else slab_len
+        b.stride, b.data_off = frames.stride, frames.data_off
+        b.offsets = frames.offsets.data_ptr() if frames.offsets is not None else None
+        io = acl_io(acl, self._ptr, in_lport, lports, n_bins, sel=sel, length=length)
+        N.check(self._L.cndp_gpu_acl_fwd(self.h, table.h, ctypes.byref(b), mode,
+                                         N.CNDP_ACL_F_MAC_SWAP if swap else 0, ctypes.byref(io), stream or None),
+                "cndp_gpu_acl_fwd")
+        acl["n_bins"] = n_bins
+        return acl
+
     def bin_partition(self, bin_of, n_bins: int, stream: int | None = None):
         """Stable partition of packet indices by bin id (per-edge streams)."""
         import torch

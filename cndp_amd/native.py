@@ -1,6 +1,7 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
-include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h and include/cndp_tx.h).
+include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h
+and include/cndp_acl.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -120,6 +121,17 @@ CNDP_TX_EDGE_NONE = 0xFFFF
 (CNDP_TX_STAT_SENT, CNDP_TX_STAT_ARP_REQUEST, CNDP_TX_STAT_DROP_HEADROOM, CNDP_TX_STAT_DROP_NOROUTE,
  CNDP_TX_STAT_DROP_PROTO, CNDP_TX_STAT_CKSUM) = range(6)
 CNDP_TX_NSTATS = 6
+
+# cndp_acl.h
+CNDP_ACL_MAX_RULES = 100000
+CNDP_ACL_DENY_SIGNATURE = 0xF0000000
+CNDP_ACL_INIT_RULES = 4226
+CNDP_ACL_STRICT, CNDP_ACL_PERMISSIVE = 0, 1
+CNDP_ACL_F_MAC_SWAP = 1
+CNDP_ACL_NONE, CNDP_ACL_PREFILTER, CNDP_ACL_DENY, CNDP_ACL_FORWARD = range(4)
+CNDP_ACL_LPORT_NONE = 0xFF
+CNDP_ACL_STAT_PREFILTER_DROP, CNDP_ACL_STAT_DENY, CNDP_ACL_STAT_PERMIT = range(3)
+CNDP_ACL_NSTATS = 3
 
 
 def CNDP_L4_EDGE(node: int, e: int) -> int:
@@ -242,6 +254,19 @@ class TxIo(Structure):
     """struct cndp_tx_io (cndp_tx.h)."""
     _fields_ = [("sel", c_void_p), ("pcb", c_void_p), ("faddr", c_void_p), ("laddr", c_void_p),
                 ("ports", c_void_p), ("len", c_void_p), ("tx_edge", c_void_p), ("bin_of", c_void_p),
+                ("n_bins", c_uint32), ("stats", c_void_p)]
+
+
+class AclRule(Structure):
+    """struct cndp_acl_rule (cndp_acl.h)."""
+    _fields_ = [("src_addr", c_uint32), ("dst_addr", c_uint32), ("src_msk", c_uint8), ("dst_msk", c_uint8),
+                ("deny", c_uint8), ("rsvd", c_uint8)]
+
+
+class AclIo(Structure):
+    """struct cndp_acl_io (cndp_acl.h)."""
+    _fields_ = [("sel", c_void_p), ("len", c_void_p), ("in_lport", c_uint32), ("lport_mask", c_uint64 * 4),
+                ("result", c_void_p), ("verdict", c_void_p), ("tx_lport", c_void_p), ("bin_of", c_void_p),
                 ("n_bins", c_uint32), ("stats", c_void_p)]
 
 
@@ -388,6 +413,17 @@ def lib():
                                         c_void_p]),
         "cndp_tx_output_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_uint64, c_void_p,
                                         c_uint32, c_uint32, POINTER(TxIo)]),
+        # cndp_acl.h
+        "cndp_acl_tbl_create": (c_int, [POINTER(c_void_p)]),
+        "cndp_acl_tbl_destroy": (None, [c_void_p]),
+        "cndp_acl_add": (c_int, [c_void_p, POINTER(AclRule)]),
+        "cndp_acl_clear": (c_int, [c_void_p]),
+        "cndp_acl_count": (c_int, [c_void_p]),
+        "cndp_acl_get": (c_int, [c_void_p, c_uint32, POINTER(AclRule)]),
+        "cndp_acl_add_init_rules": (c_int, [c_void_p]),
+        "cndp_acl_build": (c_int, [c_void_p]),
+        "cndp_gpu_acl_fwd": (c_int, [c_void_p, c_void_p, POINTER(Batch), c_uint32, c_uint32, POINTER(AclIo), c_void_p]),
+        "cndp_acl_classify_host": (c_int, [c_void_p, POINTER(Batch), c_uint32, c_uint32, POINTER(AclIo)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
