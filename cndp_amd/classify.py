@@ -295,6 +295,36 @@ class Classifier:
         acl["n_bins"] = n_bins
         return acl
 
+    def cndpfwd(self, frames, mode: int, fib=None, in_lport: int = 0, lports=(), sel=None,
+                n_bins: int | None = None, stream: int | None = None, out: dict | None = None,
+                slab_len: int | None = None) -> dict:
+        """cndpfwd's fwd / l3fwd mode (cndp_gpu_cfwd, include/cndp_cfwd.h) over
+        every frame (or those with sel[i] != 0), edited in place: `mode` is
+        CNDP_CFWD_FWD or CNDP_CFWD_L3FWD, `fib` the l3fwd FIB (8-byte entries;
+        not needed in FWD mode), `lports` the ports that exist, `in_lport` the
+        one the frames came in on.  Returns the stage's outputs as tensors (nh,
+        tx_lport, echoed, bin_of, stats; stats accumulates when a previous
+        result is passed back as `out`)."""
+        import torch
+        from .cfwd import alloc_cfwd_outputs, cfwd_io, default_n_bins
+        dev = frames.slab.device
+        if out is None:
+            out = alloc_cfwd_outputs(frames.n, dev)
+        if n_bins is None:
+            n_bins = default_n_bins(in_lport, lports)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        b = N.Batch()
+        b.n, b.slab = frames.n, frames.slab.data_ptr()
+        b.slab_len = frames.slab.numel() if slab_len is None else slab_len
+        b.stride, b.data_off = frames.stride, frames.data_off
+        b.offsets = frames.offsets.data_ptr() if frames.offsets is not None else None
+        io = cfwd_io(out, self._ptr, in_lport, lports, n_bins, sel=sel)
+        N.check(self._L.cndp_gpu_cfwd(self.h, fib.h if fib is not None else None, ctypes.byref(b), mode,
+                                      ctypes.byref(io), stream or None), "cndp_gpu_cfwd")
+        out["n_bins"] = n_bins
+        return out
+
     def bin_partition(self, bin_of, n_bins: int, stream: int | None = None):
         """Stable partition of packet indices by bin id (per-edge streams)."""
         import torch

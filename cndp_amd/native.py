@@ -1,7 +1,7 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
-include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h
-and include/cndp_acl.h).
+include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h,
+include/cndp_acl.h and include/cndp_cfwd.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -132,6 +132,14 @@ CNDP_ACL_NONE, CNDP_ACL_PREFILTER, CNDP_ACL_DENY, CNDP_ACL_FORWARD = range(4)
 CNDP_ACL_LPORT_NONE = 0xFF
 CNDP_ACL_STAT_PREFILTER_DROP, CNDP_ACL_STAT_DENY, CNDP_ACL_STAT_PERMIT = range(3)
 CNDP_ACL_NSTATS = 3
+# cndp_cfwd.h
+CNDP_CFWD_FWD, CNDP_CFWD_L3FWD = 0, 1
+CNDP_CFWD_DEFAULT_NH = 0xFFFFFFFFFFFF
+CNDP_CFWD_MAX_ROUTES = 1 << 16
+CNDP_CFWD_PORT_MAX = 0x7FFF
+CNDP_CFWD_LPORT_NONE = 0xFFFF
+CNDP_CFWD_STAT_FORWARD, CNDP_CFWD_STAT_ECHO = range(2)
+CNDP_CFWD_NSTATS = 2
 
 
 def CNDP_L4_EDGE(node: int, e: int) -> int:
@@ -268,6 +276,13 @@ class AclIo(Structure):
     _fields_ = [("sel", c_void_p), ("len", c_void_p), ("in_lport", c_uint32), ("lport_mask", c_uint64 * 4),
                 ("result", c_void_p), ("verdict", c_void_p), ("tx_lport", c_void_p), ("bin_of", c_void_p),
                 ("n_bins", c_uint32), ("stats", c_void_p)]
+
+
+class CfwdIo(Structure):
+    """struct cndp_cfwd_io (cndp_cfwd.h)."""
+    _fields_ = [("sel", c_void_p), ("in_lport", c_uint32), ("lport_mask", c_uint64 * 4), ("nh", c_void_p),
+                ("tx_lport", c_void_p), ("echoed", c_void_p), ("bin_of", c_void_p), ("n_bins", c_uint32),
+                ("stats", c_void_p)]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -424,6 +439,12 @@ def lib():
         "cndp_acl_build": (c_int, [c_void_p]),
         "cndp_gpu_acl_fwd": (c_int, [c_void_p, c_void_p, POINTER(Batch), c_uint32, c_uint32, POINTER(AclIo), c_void_p]),
         "cndp_acl_classify_host": (c_int, [c_void_p, POINTER(Batch), c_uint32, c_uint32, POINTER(AclIo)]),
+        # cndp_cfwd.h
+        "cndp_cfwd_fib_create": (c_void_p, [c_char_p]),
+        "cndp_cfwd_nexthop": (c_uint64, [c_void_p, c_uint16]),
+        "cndp_cfwd_route_add": (c_int, [c_void_p, c_uint32, c_uint8, c_void_p, c_uint16]),
+        "cndp_gpu_cfwd": (c_int, [c_void_p, c_void_p, POINTER(Batch), c_uint32, POINTER(CfwdIo), c_void_p]),
+        "cndp_cfwd_host": (c_int, [c_void_p, POINTER(Batch), c_uint32, POINTER(CfwdIo)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
