@@ -80,6 +80,15 @@ def do_options(rd, optlen: int, flags: int, max_mss: int, now: int):
     return ts_val, ts_ecr, mss, sflags | scale
 
 
+def predic_entry(tcb, flags: int, sq: int, wnd: int, sflags: int, ts_val: int) -> bool:
+    """The header-prediction entry test, inline in cnet_tcp_input (:3473-3482);
+    wnd is the window after scaling."""
+    ts = sflags & TS_PRESENT
+    return bool(tcb["state"] == ESTABLISHED and (flags & HDR_PREDIC) == ACK
+                and (not ts or s32(ts_val - tcb["ts_recent"]) >= 0)
+                and sq == tcb["rcv_nxt"] and wnd and wnd == tcb["snd_wnd"] and tcb["snd_nxt"] == tcb["snd_max"])
+
+
 def segment_one(tcb, seg, rd, now: int):
     """One segment against its PCB's TCB (a dict of struct cndp_tcb's fields, or
     None): (verdict | TS_UPDATE, opt tuple)."""
@@ -100,9 +109,7 @@ def segment_one(tcb, seg, rd, now: int):
     opt = (ts_val, ts_ecr, wnd, mss, sflags)
     sq, ak, ln = int(seg["seq"]), int(seg["ack"]), int(seg["len"])
     ts = sflags & TS_PRESENT
-    if not (tcb["state"] == ESTABLISHED and (flags & HDR_PREDIC) == ACK
-            and (not ts or s32(ts_val - tcb["ts_recent"]) >= 0)
-            and sq == tcb["rcv_nxt"] and wnd and wnd == tcb["snd_wnd"] and tcb["snd_nxt"] == tcb["snd_max"]):
+    if not predic_entry(tcb, flags, sq, wnd, sflags, ts_val):
         return SLOW, opt
     upd = TS_UPDATE if ts and s32(ts_val - tcb["ts_recent"]) <= 0 and s32(tcb["last_ack_sent"] - sq) < 0 else 0
     if ln == 0:
@@ -154,9 +161,10 @@ def _fold(b: bytes) -> int:
 
 
 def frame_bytes(spec: dict) -> bytes:
-    """Ethernet + IPv4 (IHL 5) + TCP for one spec: pair, seq, ack, wnd, flags,
-    opts (any bytes, a multiple of 4, at most 40), payload (bytes), urp,
-    bad_cksum."""
+    """Ethernet + IPv4 + TCP for one spec: pair, seq, ack, wnd, flags, opts (any
+    bytes, a multiple of 4, at most 40), payload (bytes), urp, bad_cksum, ihl
+    (5..15, default 5: the words past 5 are NOP IP options, and the header
+    checksum covers the whole header)."""
     (dst, dport), (src, sport) = spec.get("pair", PAIR)
     opts, payload = bytes(spec.get("opts", b"")), bytes(spec.get("payload", b""))
     assert len(opts) % 4 == 0 and len(opts) <= 40
@@ -164,9 +172,11 @@ def frame_bytes(spec: dict) -> bytes:
                     + (spec["ack"] & M32).to_bytes(4, "big") + bytes([(5 + len(opts) // 4) << 4, spec["flags"]])
                     + (spec["wnd"] & 0xFFFF).to_bytes(2, "big") + b"\0\0"
                     + (spec.get("urp", 0) & 0xFFFF).to_bytes(2, "big") + opts + payload)
-    ip = bytearray(20)
-    ip[0], ip[8], ip[9] = 0x45, 64, 6
-    ip[2:4] = (20 + len(tcp)).to_bytes(2, "big")
+    ihl = spec.get("ihl", 5)
+    assert 5 <= ihl <= 15
+    ip = bytearray(20) + bytes([1]) * (4 * ihl - 20)
+    ip[0], ip[8], ip[9] = 0x40 | ihl, 64, 6
+    ip[2:4] = (4 * ihl + len(tcp)).to_bytes(2, "big")
     ip[12:16], ip[16:20] = src.to_bytes(4, "big"), dst.to_bytes(4, "big")
     ip[10:12] = ((~_fold(bytes(ip))) & 0xFFFF).to_bytes(2, "big")
     c = (~_fold(bytes(ip[12:20]) + bytes([0, 6]) + len(tcp).to_bytes(2, "big") + bytes(tcp))) & 0xFFFF
@@ -208,7 +218,7 @@ def build(specs, layout: str = "offsets", slot: int = 128, align: int = 1) -> di
         o = int(offs[i]) + data_off
         slab[o:o + len(f)] = np.frombuffer(f, np.uint8)
     return {"slab": slab, "offsets": offs.astype(np.uint64) if layout == "offsets" else None, "stride": stride,
-            "data_off": data_off, "rxmeta": np.full(n, 14 | 20 << 7, np.uint32),
+            "data_off": data_off, "rxmeta": np.array([14 | 4 * s.get("ihl", 5) << 7 for s in specs], np.uint32).reshape(n),
             "seg": np.array([seg_of(s) for s in specs], SEG_DT).reshape(n), "n": n}
 
 

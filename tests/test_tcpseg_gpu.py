@@ -5,7 +5,10 @@ Python restatement (tests/tcpseg_ref.py) applied to the same arrays, for every
 frame.  Shapes are the smallest that can still go wrong: one frame, a wave and
 its neighbours, more than one 256-lane block (and more than one 1024-lane block
 of tcp_input); packed slots, the UMEM stride, odd byte offsets; tables of 1, 513
-and 4096 connections; options that end with the slab."""
+and 4096 connections; options that end with the slab.  The last three tests
+hold the stage against recorded outputs of the compiled reference
+(tests/golden/tcp_options_ref.npz, tests/tcp_golden.py) and put IP options in
+front of the TCP header."""
 import numpy as np
 import pytest
 import torch
@@ -13,6 +16,7 @@ import torch
 from cndp_amd import native as N
 from cndp_amd.l4 import PcbTable, TcbTable, alloc_tcpseg_outputs, opt_records, seg_records
 
+import tcp_golden as TG
 import tcp_ref as T
 import tcpseg_ref as S
 from helpers import cnet_fibs
@@ -290,5 +294,90 @@ def test_errno_rules_and_empty_batch(cnet, gpu):
         res = cl.tcp_segment(fr0, {"rxmeta": out["rxmeta"][:0]}, co.tcbs, {k: tcp[k][:0] for k in ("l4edge", "pcb", "seg")})
         torch.cuda.synchronize()
         assert res["stats"].tolist() == [0] * 8
+    finally:
+        co.close()
+
+
+# ---- against recorded outputs of the compiled reference (tests/golden/tcp_options_ref.npz) ----
+def golden_batch(cnet, cases, now, layout):
+    """One connection per case, the frames through classify -> udp_input ->
+    tcp_input -> tcp_segment in one call: what the stage gave, after segment()
+    has held it against the restatement.  Every frame must have reached the
+    SEGMENT edge on its own connection, or the vector would go unjudged."""
+    co = Conns(cnet[1], len(cases))
+    try:
+        specs = []
+        for i, (tcb, spec) in enumerate(cases):
+            co.set(i, tcb)
+            specs.append(dict(spec, pair=co.pair(i)))
+        fr, out, tcp = upstream(cnet, co, specs, layout)
+        assert (host(tcp["l4edge"], np.uint8) == T.E_SEG).all()
+        assert (host(tcp["pcb"], np.uint32) == np.arange(len(cases))).all()
+        got, _, _ = segment(cnet, co, fr, out, tcp, now)
+        assert ((got["verdict"] & S.FIRST) != 0).all() and got["stats"].sum() == len(cases) and got["stats"][0] == 0
+        return got
+    finally:
+        co.close()
+
+
+@pytest.mark.parametrize("layout", ["odd", "packed"])
+def test_reference_option_vectors(cnet, gpu, layout):
+    """The parse vectors of the golden file, one call per recorded `now`: BADOPT
+    exactly where the compiled tcp_do_options returned -1, and its ts_val,
+    ts_ecr, mss and sflags | req_scale where it returned 0.  In the odd layout
+    the option bytes start at every byte alignment, so both of rd_words' paths
+    run; each frame's one payload byte is the recorded byte behind the options."""
+    G = TG.load()
+    seen = 0
+    for k, now in enumerate(G["nows"].tolist()):
+        idx, cases = TG.parse_cases(G, k)
+        got = golden_batch(cnet, cases, now, layout)
+        TG.parse_check(G, idx, got["verdict"], got["opt"], f"GPU, {layout}, now {now:#x}")
+        seen += len(idx)
+    assert seen == len(G["p_tail"]) and seen <= 4096
+
+
+@pytest.mark.parametrize("layout", ["odd", "packed"])
+def test_reference_prediction_vectors(cnet, gpu, layout):
+    """The prediction vectors: the branch tcp_header_prediction took (ack / data /
+    neither) and whether it took ts_recent, as recorded.  The entry test in front
+    of it is inline in cnet_tcp_input and stays restated: every vector passes it
+but eight hand-built ones with ts_val = ts_recent - 1, which must come out SLOW."""
+    G = TG.load()
+    seen = 0
+    for k, now in enumerate(G["nows"].tolist()):
+        idx, cases = TG.pred_cases(G, k)
+        if len(idx):
+            got = golden_batch(cnet, cases, now, layout)
+            TG.pred_check(G, idx, got["verdict"], got["opt"], f"GPU, {layout}, now {now:#x}")
+            seen += len(idx)
+    assert seen == len(G["h_branch"]) and seen <= 4096
+
+
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_ip_options_in_front_of_tcp(cnet, gpu, layout):
+    """65 pure ACKs with IHL 5, 6 and 15 mixed: the option bytes are at
+    L2 + L3 + 20 with L3 up to 60, which needs all of CNDP_RXMETA_L3's bits.  The
+    ptype node has no ip4_input edge for IPV4_EXT | TCP (the checker says so in
+    test_tcp_reference_golden.py, and the stages say so here), so such frames
+    never reach the SEGMENT edge by themselves: tcp_input is run again with
+    sel=, over the rxmeta classify wrote, and tcp_segment takes what it left."""
+    cl = cnet[0]
+    cases = TG.ip_option_cases()
+    co = Conns(cnet[1], len(cases))
+    try:
+        specs = []
+        for i, (tcb, spec) in enumerate(cases):
+            co.set(i, tcb)
+            specs.append(dict(spec, pair=co.pair(i)))
+        fr, out, tcp = upstream(cnet, co, specs, layout)
+        ihl = np.array([s["ihl"] for s in specs])
+        assert ((host(tcp["l4edge"], np.uint8) == T.E_SEG) == (ihl == 5)).all()
+        assert (host(out["rxmeta"], np.uint32) & 0xFFFF == (14 | ihl * 4 << 7)).all()
+        tcp = cl.tcp_input(fr, out, co.pcbs, sel=torch.ones(fr.n, dtype=torch.uint8, device=fr.slab.device))
+        torch.cuda.synchronize()
+        assert (host(tcp["l4edge"], np.uint8) == T.E_SEG).all() and (host(tcp["pcb"], np.uint32) == np.arange(fr.n)).all()
+        got, _, _ = segment(cnet, co, fr, out, tcp, 1000)
+        TG.ip_option_check(got["verdict"], got["opt"])
     finally:
         co.close()
