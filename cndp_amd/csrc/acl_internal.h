@@ -164,6 +164,17 @@ static inline ACL_HD uint32_t acl_tx_lport(uint32_t dmac5, uint64_t m0, uint64_t
 /* argument checks shared by the host twin and the GPU call: 0 or -EINVAL */
 int acl_io_check(const struct cndp_batch *b, uint32_t mode, uint32_t flags, const struct cndp_acl_io *io);
 
+/* The device mirror's reader protocol (cndp_acl.hip), for a launch that reads
+ * the image on `stream` of device `dev`: acl_dev_begin takes t->lock, answers
+ * -ENOENT for a table without an image, binds the device, makes `stream` wait
+ * for the last reader when that was another stream, brings the mirror up to
+ * date and hands out the image's device address.  It returns 0 with t->lock
+ * HELD, or a negative errno with the lock released.  acl_dev_end, called after
+ * the launch is enqueued (launched != 0) or given up (0), records the reader's
+ * end on `stream` for the next call and releases the lock. */
+int acl_dev_begin(struct cndp_acl_tbl *t, int dev, void *stream, const uint32_t **img, int *cus);
+int acl_dev_end(struct cndp_acl_tbl *t, void *stream, int launched);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,11 @@
 //                   Counters: a ballot per verdict per wave, an LDS add per
 //                   wave, one global add per block and counter.
 // Every frame read is bounded by slab_len; no load or store leaves the slab.
+//
+// The image's device mirror is one buffer, overwritten in place by a rebuild and
+// guarded by an event.  Every reader -- cndp_gpu_acl_fwd here, the mbuf queue's
+// CNDP_MQ_ACL_FWD kernel in cndp_gpu.hip -- brackets its launch with
+// acl_dev_begin / acl_dev_end (acl_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
@@ -300,14 +305,55 @@ static int acl_mirror(AclDev *d, struct cndp_acl_tbl *t, hipStream_t s)
     return 0;
 }
 
-static int acl_run(AclDev *d, struct cndp_acl_tbl *t, const struct cndp_batch *b, uint32_t mode, uint32_t flags,
-                   const struct cndp_acl_io *io, hipStream_t s)
+// acl_dev_begin under t->lock: the device, the wait for a reader on another stream, the mirror
+static int acl_begin_locked(struct cndp_acl_tbl *t, int dev, hipStream_t s, AclDev **out)
 {
+    if (!t->img)
+        return -ENOENT;
+    HIP_TRY(hipSetDevice(dev));
+    AclDev *d = NULL;
+    int r = acl_dev_get(t, dev, &d);
+    if (r)
+        return r;
     if (d->have_last && d->last != s)
         HIP_TRY(hipStreamWaitEvent(s, d->ev, 0));
-    int r = acl_mirror(d, t, s);
-    if (r || b->n == 0)
+    *out = d;
+    return acl_mirror(d, t, s);
+}
+
+extern "C" int acl_dev_begin(struct cndp_acl_tbl *t, int dev, void *stream, const uint32_t **img, int *cus)
+{
+    pthread_mutex_lock(&t->lock);
+    AclDev *d = NULL;
+    const int r = acl_begin_locked(t, dev, (hipStream_t)stream, &d);
+    if (r) {
+        pthread_mutex_unlock(&t->lock);
         return r;
+    }
+    *img = d->img;
+    if (cus)
+        *cus = d->cus;
+    return 0;
+}
+
+static int acl_end_locked(AclDev *d, hipStream_t s)
+{
+    HIP_TRY(hipEventRecord(d->ev, s));
+    d->last = s;
+    d->have_last = 1;
+    return 0;
+}
+
+extern "C" int acl_dev_end(struct cndp_acl_tbl *t, void *stream, int launched)
+{
+    const int r = launched ? acl_end_locked((AclDev *)t->dev, (hipStream_t)stream) : 0;
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+static int acl_launch(int cus, const uint32_t *img, const struct cndp_batch *b, uint32_t mode, uint32_t flags,
+                      const struct cndp_acl_io *io, hipStream_t s)
+{
     AclArgs a;
     a.slab = (uint8_t *)(uintptr_t)b->slab;
     a.slab_len = b->slab_len;
@@ -332,13 +378,10 @@ static int acl_run(AclDev *d, struct cndp_acl_tbl *t, const struct cndp_batch *b
     a.swap = flags & CNDP_ACL_F_MAC_SWAP;
 
     const uint64_t want = ((uint64_t)b->n + ACL_BLOCK - 1u) / ACL_BLOCK;
-    const uint64_t cap = (uint64_t)d->cus * ACL_BLOCKS_PER_CU;
+    const uint64_t cap = (uint64_t)cus * ACL_BLOCKS_PER_CU;
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
-    hipLaunchKernelGGL(acl_fwd_kernel, dim3(grid), dim3(ACL_BLOCK), 0, s, a, (const uint32_t *)d->img);
+    hipLaunchKernelGGL(acl_fwd_kernel, dim3(grid), dim3(ACL_BLOCK), 0, s, a, img);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev, s));
-    d->last = s;
-    d->have_last = 1;
     return 0;
 }
 
@@ -350,13 +393,12 @@ extern "C" int cndp_gpu_acl_fwd(cndp_gpu_ctx_t *ctx, cndp_acl_tbl_t *t, const st
     int r = acl_io_check(b, mode, flags, io);
     if (r)
         return r;
-    const int dev = cndp_gpu_device(ctx);
-    HIP_TRY(hipSetDevice(dev));
-    pthread_mutex_lock(&t->lock);
-    AclDev *d = NULL;
-    r = t->img ? acl_dev_get(t, dev, &d) : -ENOENT;
-    if (!r)
-        r = acl_run(d, t, b, mode, flags, io, (hipStream_t)stream);
-    pthread_mutex_unlock(&t->lock);
-    return r;
+    const uint32_t *img = NULL;
+    int cus = 0;
+    if ((r = acl_dev_begin(t, cndp_gpu_device(ctx), stream, &img, &cus)))
+        return r;
+    if (b->n)
+        r = acl_launch(cus, img, b, mode, flags, io, (hipStream_t)stream);
+    const int e = acl_dev_end(t, stream, b->n && !r);
+    return r ? r : e;
 }

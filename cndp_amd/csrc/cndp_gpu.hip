@@ -32,6 +32,9 @@
 #include "node_internal.h"
 #include "../../include/cndp_gpu.h"
 #include "../../include/cndp_l4.h" // CNDP_PCB_MAX_ENTRIES
+#include "acl_internal.h"           // the cndpfwd queue modes' per-frame rules
+#include "cfwd_internal.h"
+#include "../../include/cndp_mqfwd.h"
 
 #define CNDP_VERSION "cndp_amd 0.1 (gfx950)"
 
@@ -7423,6 +7426,233 @@ __global__ __launch_bounds__(MQ_TPB) void k_mq_mac_swap(MqArgs a)
     mq_complete(a);
 }
 
+// cndpfwd's fwd, l3fwd and ACL modes (cndp_mqfwd.h): one mbuf per lane, the
+// frame where the mbuf says it is -- zero-copy in its registered region, with
+// the frame word's readable count as the bound; staged in the slot's staging
+// (MQ_SWAP bytes for fwd, MQ_FWD_STAGE for l3fwd and acl, zero-filled past the
+// buffer), whose changed bytes poll copies back.  The rules are cfwd_rule
+// (cfwd_internal.h) and acl_prefilter / acl_decide / acl_tx_lport and the
+// image walk of acl_internal.h, the text the host twins and the batch kernels
+// (cndp_cfwd.hip, cndp_acl.hip) run.  A 4-byte aligned frame with its first 36
+// bytes readable (fwd: 12, all it reads) takes dword loads and stores, any
+// other frame bounded byte accesses with the same results: bytes past the
+// readable count read as zero and are never written.  No counters here: poll
+// counts from the edges.
+#define MQ_FWD_STAGE 48u // l3fwd / acl: staged bytes (they read up to byte 33)
+#define MQ_FWD_WIDE 36u  // readable bytes the dword path of l3fwd / acl needs
+#define MQ_ACL_AHEAD 4u  // acl: groups whose first slot is in flight at once (ACL_AHEAD of cndp_acl.hip)
+
+struct MqFwd { // what these kernels take beside MqArgs (in_lport is MqArgs.lport)
+    uint64_t m0, m1, m2, m3; // lport_mask
+    uint32_t acl_mode, acl_swap;
+};
+
+// byte k of a frame with `avail` readable bytes, zero at or past them
+__device__ __forceinline__ uint32_t mqf_byte(const uint8_t *p, uint32_t avail, uint32_t k)
+{
+    return k < avail ? p[k] : 0u;
+}
+
+__device__ __forceinline__ uint32_t mqf_le32(const uint8_t *p, uint32_t avail, uint32_t k)
+{
+    return mqf_byte(p, avail, k) | mqf_byte(p, avail, k + 1u) << 8 | mqf_byte(p, avail, k + 2u) << 16 |
+           mqf_byte(p, avail, k + 3u) << 24;
+}
+
+// the low CNT bytes of v to frame bytes k ..., those below avail
+template <uint32_t CNT>
+__device__ __forceinline__ void mqf_store(uint8_t *p, uint32_t avail, uint32_t k, uint32_t v)
+{
+#pragma unroll
+    for (uint32_t j = 0; j < CNT; j++)
+        if (k + j < avail)
+            p[k + j] = (uint8_t)(v >> (8u * j));
+}
+
+// mbuf i's frame and its readable bytes (nullptr: zero-copy, outside every region)
+__device__ __forceinline__ uint8_t *mq_fwd_frame(const MqArgs &a, uint32_t i, uint32_t stage, uint32_t &avail)
+{
+    if (a.zc)
+        return mq_frame(a.off[i], avail);
+    avail = stage;
+    return (uint8_t *)a.slab + a.off[i];
+}
+
+// _fwd_test (main.c:164-206) / _l3fwd_test (main.c:257-314) per mbuf: edge =
+// tx_lport, CNDP_MQ_EDGE_ECHO OR-ed in for a frame that goes back to in_lport.
+// cfwd_rule issues the tbl24 gather before the TTL / checksum arithmetic; the
+// table pointers are restrict arguments so the frame stores do not stand in
+// the gathers' way.
+template <uint32_t MODE>
+__global__ __launch_bounds__(MQ_TPB) void k_mq_cfwd(MqArgs a, MqFwd w, const uint64_t *__restrict__ t24,
+                                                    const uint64_t *__restrict__ t8)
+{
+    constexpr bool l3 = MODE == CNDP_CFWD_L3FWD;
+    for (uint32_t i = blockIdx.x * MQ_TPB + threadIdx.x; i < a.n; i += gridDim.x * MQ_TPB) {
+        uint32_t avail;
+        uint8_t *p = mq_fwd_frame(a, i, l3 ? MQ_FWD_STAGE : MQ_SWAP, avail);
+        if (p == nullptr) {
+            a.edges[i] = (uint16_t)MQ_EDGE_NONE;
+            continue;
+        }
+        const bool wide = (((uintptr_t)p) & 3u) == 0 && avail >= (l3 ? MQ_FWD_WIDE : 12u);
+        struct cfwd_frame f;
+        struct cfwd_edit e;
+        uint32_t d5 = 0, d6 = 0;
+        if (wide) {
+            const uint32_t *d = (const uint32_t *)p;
+            f.d0 = d[0], f.d1 = d[1], f.d2 = d[2];
+            if (l3) {
+                d5 = d[5], d6 = d[6];
+                const uint32_t d7 = d[7], d8 = d[8];
+                f.ttl = (d5 >> 16) & 0xffu; // byte 22
+                f.ck = d6 & 0xffffu;        // bytes 24, 25
+                f.dst = alignb(d8, d7, 2);  // bytes 30..33
+            } else {
+                f.ttl = f.ck = f.dst = 0;
+            }
+        } else {
+            f.d0 = mqf_le32(p, avail, 0);
+            f.d1 = mqf_le32(p, avail, 4);
+            f.d2 = mqf_le32(p, avail, 8);
+            if (l3) {
+                f.ttl = mqf_byte(p, avail, 22);
+                f.ck = mqf_byte(p, avail, 24) | mqf_byte(p, avail, 25) << 8;
+                f.dst = mqf_le32(p, avail, 30);
+            } else {
+                f.ttl = f.ck = f.dst = 0;
+            }
+        }
+        cfwd_rule(MODE, &f, t24, t8, w.m0, w.m1, w.m2, w.m3, a.lport, &e);
+        const bool all12 = !l3 || e.echo; // MAC_SWAP: bytes 0-11; MAC_REWRITE: bytes 0-5
+        if (wide) {
+            // whole dwords, the bytes that do not change (6-7 of a rewrite, 20-21, 23, 26-27)
+            // with the values just read
+            uint32_t *d = (uint32_t *)p;
+            d[0] = e.d0;
+            d[1] = e.d1;
+            if (all12)
+                d[2] = e.d2;
+            if (l3) {
+                d[5] = (d5 & 0xFF00FFFFu) | e.ttl << 16;
+                d[6] = (d6 & 0xFFFF0000u) | e.ck;
+            }
+        } else {
+            mqf_store<4>(p, avail, 0, e.d0);
+            if (all12) {
+                mqf_store<4>(p, avail, 4, e.d1);
+                mqf_store<4>(p, avail, 8, e.d2);
+            } else {
+                mqf_store<2>(p, avail, 4, e.d1);
+            }
+            if (l3) {
+                mqf_store<1>(p, avail, 22, e.ttl);
+                mqf_store<2>(p, avail, 24, e.ck);
+            }
+        }
+        a.edges[i] = (uint16_t)(e.tx | (e.echo ? CNDP_MQ_EDGE_ECHO : 0u));
+    }
+    mq_complete(a);
+}
+
+// acl_fwd_test (acl-func.c:310-402) per mbuf: validate_ipv4_pkt with
+// m->data_len as the host read it at submit (a.priv), the classify over the
+// image, the decision, and for a forwarded frame the destination port and --
+// with CNDP_ACL_F_MAC_SWAP -- MAC_SWAP.  edge = tx_lport, or
+// CNDP_MQ_EDGE_ACL_DENY / _ACL_PREFILTER.  The group walk is acl_fwd_kernel's
+// (cndp_acl.hip): the loop runs on a wave-uniform counter over whole waves
+// (lanes past n or without a frame ride along inactive), so the descriptors
+// are scalar loads; MQ_ACL_AHEAD groups' first slots are fetched together and
+// the loop ends when a ballot says no lane can still improve.
+__global__ __launch_bounds__(MQ_TPB) void k_mq_acl(MqArgs a, MqFwd w, const uint32_t *__restrict__ img)
+{
+    const uint32_t ng = img[1];
+    for (uint32_t base = blockIdx.x * MQ_TPB; base < a.n; base += gridDim.x * MQ_TPB) {
+        const uint32_t i = base + threadIdx.x;
+        const bool live = i < a.n;
+        uint32_t avail = 0;
+        uint8_t *p = live ? mq_fwd_frame(a, i, MQ_FWD_STAGE, avail) : nullptr;
+        const bool taken = p != nullptr;
+        uint32_t dmac5 = 0, w0 = 0, src = 0, dst = 0;
+        bool len_ok = true;
+        if (taken) {
+            len_ok = a.priv[i] >= 20u;
+            if ((((uintptr_t)p) & 3u) == 0 && avail >= MQ_FWD_WIDE) {
+                const uint32_t *d = (const uint32_t *)p;
+                const uint32_t d1 = d[1], d3 = d[3], d4 = d[4], d6 = d[6], d7 = d[7], d8 = d[8];
+                dmac5 = (d1 >> 8) & 0xffu;
+                w0 = alignb(d4, d3, 2);  // bytes 14..17
+                src = alignb(d7, d6, 2); // bytes 26..29
+                dst = alignb(d8, d7, 2); // bytes 30..33
+            } else {
+                dmac5 = mqf_byte(p, avail, 5);
+                w0 = mqf_le32(p, avail, 14);
+                src = mqf_le32(p, avail, 26);
+                dst = mqf_le32(p, avail, 30);
+            }
+        }
+        const bool act = taken && !acl_prefilter(w0, len_ok);
+        src = bswap32(src);
+        dst = bswap32(dst);
+        uint32_t best = 0;
+        for (uint32_t g0 = 0; g0 < ng; g0 += MQ_ACL_AHEAD) {
+            const uint32_t *d0 = img + ACL_HDR_WORDS + g0 * ACL_DESC_WORDS;
+            const bool go = act && !acl_done(d0, best);
+            if (!__ballot(go))
+                break; // no lane of the wave can still improve: the groups ascend
+            uint32_t h[MQ_ACL_AHEAD], s0[MQ_ACL_AHEAD], s1[MQ_ACL_AHEAD], v[MQ_ACL_AHEAD];
+#pragma unroll
+            for (uint32_t k = 0; k < MQ_ACL_AHEAD; k++) {
+                // every lane loads, whatever `go` says, and a k past the last group repeats the
+                // last one; any h gives a slot inside the group's table
+                const uint32_t *d = img + ACL_HDR_WORDS + (g0 + k < ng ? g0 + k : ng - 1u) * ACL_DESC_WORDS;
+                h[k] = acl_hash(src & d[0], dst & d[1]);
+                acl_slot(img, d, h[k], &s0[k], &s1[k], &v[k]);
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < MQ_ACL_AHEAD; k++) {
+                const uint32_t *d = img + ACL_HDR_WORDS + (g0 + k < ng ? g0 + k : ng - 1u) * ACL_DESC_WORDS;
+                const uint32_t ks = src & d[0], kd = dst & d[1];
+                const bool on = g0 + k < ng && go && !acl_done(d, best);
+                const bool hit = !v[k] || (s0[k] == ks && s1[k] == kd);
+                uint32_t e = v[k];
+                if (on && !hit) // another key sits in the first slot: walk on
+                    e = acl_probe_on(img, d, ks, kd, h[k]);
+                best = on ? acl_better(best, e) : best;
+            }
+        }
+        if (!live)
+            continue;
+        uint32_t edge = MQ_EDGE_NONE;
+        if (taken && !act) {
+            edge = CNDP_MQ_EDGE_ACL_PREFILTER;
+        } else if (taken) {
+            edge = CNDP_MQ_EDGE_ACL_DENY;
+            if (acl_decide(acl_userdata(best), w.acl_mode) == CNDP_ACL_FORWARD) {
+                edge = acl_tx_lport(dmac5, w.m0, w.m1, w.m2, w.m3, a.lport);
+                // act => byte 14 was readable, so avail >= 12; tested all the same
+                if (w.acl_swap && avail >= 12u) {
+                    if ((((uintptr_t)p) & 3u) == 0) {
+                        uint32_t *d = (uint32_t *)p;
+                        const uint32_t d0 = d[0], d1 = d[1], d2 = d[2];
+                        d[0] = alignb(d2, d1, 2);       // bytes 6..9
+                        d[1] = (d2 >> 16) | (d0 << 16); // bytes 10, 11, 0, 1
+                        d[2] = alignb(d1, d0, 2);       // bytes 2..5
+                    } else {
+                        for (int k = 0; k < 6; k++) {
+                            const uint8_t t = p[k];
+                            p[k] = p[6 + k];
+                            p[6 + k] = t;
+                        }
+                    }
+                }
+            }
+        }
+        a.edges[i] = (uint16_t)edge;
+    }
+    mq_complete(a);
+}
+
 // ip4_rewrite_node_process (ip4_rewrite.c:40-247) per packet of the node's
 // bursts: the next hop's rewrite data at mtod (:85), TTL = priv1.ttl - 1 and
 // the checksum from priv1.cksum + htons(0x0100) -- in the 4-wide loop with
@@ -7751,6 +7981,8 @@ struct cndp_gpu_mq {
     uint32_t pending;
     int err;                       // a launch error not yet reported (returned by the next submit)
     uint64_t n_batches, n_mbufs;   // launched so far (cndp_gpu_mq_stat)
+    struct cndp_mq_fwd fwd;        // cndpfwd modes (cndp_gpu_mq_create_fwd): the tables and the known ports
+    uint64_t n_fwd[CNDP_MQ_STAT_ACL_PERMIT + 1]; // their counters by CNDP_MQ_STAT_* key, counted by poll
     MqSlot slot[CNDP_MQ_DEPTH_MAX];
 };
 
@@ -7788,14 +8020,22 @@ static inline uint64_t mq_frame_word(cndp_gpu_mq_t *q, const uint8_t *f)
     return ((uint64_t)(intptr_t)(f + q->rg[k].delta) & MQ_ADDR_MASK) | ((left < 255u ? left : 255u) << 56);
 }
 
-extern "C" int cndp_gpu_mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, cndp_gpu_mq_t **out)
+static inline bool mq_is_fwd(uint32_t mode)
+{
+    return mode == CNDP_MQ_CFWD_FWD || mode == CNDP_MQ_CFWD_L3FWD || mode == CNDP_MQ_ACL_FWD;
+}
+
+// fwd: the tables of a cndpfwd mode, checked by cndp_gpu_mq_create_fwd; nullptr for the node modes
+static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const struct cndp_mq_fwd *fwd,
+                     cndp_gpu_mq_t **out)
 {
     if (!c || !conf || !out)
         return -EINVAL;
     *out = nullptr;
     struct cndp_mq_conf k = *conf;
-    if (k.mode != CNDP_MQ_IP4_LOOKUP && k.mode != CNDP_MQ_CNET && k.mode != CNDP_MQ_MAC_SWAP &&
-        k.mode != CNDP_MQ_IP4_REWRITE)
+    if (fwd ? !mq_is_fwd(k.mode)
+            : (k.mode != CNDP_MQ_IP4_LOOKUP && k.mode != CNDP_MQ_CNET && k.mode != CNDP_MQ_MAC_SWAP &&
+               k.mode != CNDP_MQ_IP4_REWRITE))
         return -EINVAL;
     if (k.flags & ~(CNDP_MQ_F_HASH | CNDP_MQ_F_NO_METADATA | CNDP_MQ_F_DEVICE_HEADERS | CNDP_MQ_F_RX_PARSE |
                     CNDP_MQ_F_REWRITE | CNDP_MQ_F_HOST_WRITEBACK))
@@ -7828,6 +8068,8 @@ extern "C" int cndp_gpu_mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *
         return -ENOMEM;
     q->c = c;
     q->conf = k;
+    if (fwd)
+        q->fwd = *fwd;
     if (k.umem) {
         // zero-copy: every region the context holds (the UMEMs of all the
         // graph's ports), conf.umem among them
@@ -7847,19 +8089,21 @@ extern "C" int cndp_gpu_mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *
     }
     const uint64_t B = k.batch;
     const bool cnet = k.mode == CNDP_MQ_CNET, rw = k.mode == CNDP_MQ_IP4_REWRITE;
+    const bool acl = k.mode == CNDP_MQ_ACL_FWD, cfwd = mq_is_fwd(k.mode);
     const bool zc = q->zc != 0;
     q->stage = zc ? 0u
              : cnet ? (uint32_t)al64(k.stage_max)
              : k.mode == CNDP_MQ_IP4_LOOKUP ? ((k.flags & CNDP_MQ_F_RX_PARSE) ? 32u : MQ_W4)
-             : k.mode == CNDP_MQ_MAC_SWAP ? MQ_SWAP : MQ_RW_STAGE;
+             : k.mode == CNDP_MQ_MAC_SWAP || k.mode == CNDP_MQ_CFWD_FWD ? MQ_SWAP
+             : cfwd ? MQ_FWD_STAGE : MQ_RW_STAGE;
     q->h_mb = 0;                                          // zc: mbuf device addresses; rewrite: tail flags
     q->h_off = al64(B * 8);                               // frame words / offsets
-    q->h_len = q->h_off + al64(B * 8);                    // cnet: length fields; rewrite: priv1
-    q->h_md = q->h_len + (cnet || rw ? al64(B * 8) : 0);  // cnet zc: metadata addresses
+    q->h_len = q->h_off + al64(B * 8);                    // cnet: length fields; rewrite: priv1; acl: data_len
+    q->h_md = q->h_len + (cnet || rw || acl ? al64(B * 8) : 0); // cnet zc: metadata addresses
     q->h_edge = q->h_md + (cnet && zc ? al64(B * 8) : 0);
     q->hostwb = zc && (k.flags & CNDP_MQ_F_HOST_WRITEBACK);
     q->h_rec = q->h_edge + al64(B * 2);                   // staged (and host writeback): records
-    q->h_rmd = q->h_rec + ((zc && !q->hostwb) || rw || k.mode == CNDP_MQ_MAC_SWAP ? 0 : al64(B * (cnet ? 16 : 8)));
+    q->h_rmd = q->h_rec + ((zc && !q->hostwb) || rw || cfwd || k.mode == CNDP_MQ_MAC_SWAP ? 0 : al64(B * (cnet ? 16 : 8)));
     q->h_stage = q->h_rmd + (q->hostwb && cnet ? B * 32 : 0); // cnet host writeback: metadata addresses
     q->h_bst = q->h_stage + B * q->stage;                 // CNDP_MQ_F_REWRITE: burst starts
     q->h_bytes = q->h_bst + ((k.flags & CNDP_MQ_F_REWRITE) ? al64((B + 1) * 4) : 0);
@@ -7901,6 +8145,46 @@ extern "C" int cndp_gpu_mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *
 fail:
     cndp_gpu_mq_free(q);
     return r;
+}
+
+extern "C" int cndp_gpu_mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, cndp_gpu_mq_t **out)
+{
+    return mq_create(c, conf, nullptr, out);
+}
+
+// cndp_mqfwd.h: the argument rules of the three cndpfwd modes, then the queue as for every mode
+extern "C" int cndp_gpu_mq_create_fwd(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf,
+                                      const struct cndp_mq_fwd *fwd, cndp_gpu_mq_t **out)
+{
+    if (!c || !conf || !fwd || !out)
+        return -EINVAL;
+    *out = nullptr;
+    if (!mq_is_fwd(conf->mode) || conf->flags || conf->lport > 255u)
+        return -EINVAL;
+    struct cndp_batch b0;
+    memset(&b0, 0, sizeof(b0));
+    if (conf->mode == CNDP_MQ_CFWD_L3FWD) { // a FIB of 8-byte entries
+        struct cndp_cfwd_io io0;
+        memset(&io0, 0, sizeof(io0));
+        const int r = cfwd_io_check(fwd->fib, &b0, CNDP_CFWD_L3FWD, &io0);
+        if (r)
+            return r;
+    }
+    if (conf->mode == CNDP_MQ_ACL_FWD) {
+        struct cndp_acl_io io0;
+        memset(&io0, 0, sizeof(io0));
+        if (!fwd->acl)
+            return -EINVAL;
+        const int r = acl_io_check(&b0, fwd->acl_mode, fwd->acl_flags, &io0);
+        if (r)
+            return r;
+        pthread_mutex_lock(&fwd->acl->lock);
+        const bool built = fwd->acl->img != nullptr;
+        pthread_mutex_unlock(&fwd->acl->lock);
+        if (!built)
+            return -ENOENT;
+    }
+    return mq_create(c, conf, fwd, out);
 }
 
 extern "C" void cndp_gpu_mq_free(cndp_gpu_mq_t *q)
@@ -8016,6 +8300,43 @@ static int mq_launch_kernels(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t slot_i)
     const uint32_t g = blocks_for(n, MQ_TPB);
     if (q->conf.mode == CNDP_MQ_MAC_SWAP) {
         hipLaunchKernelGGL(k_mq_mac_swap, dim3(g), dim3(MQ_TPB), 0, s, a);
+    } else if (mq_is_fwd(q->conf.mode)) {
+        MqFwd w;
+        w.m0 = q->fwd.lport_mask[0];
+        w.m1 = q->fwd.lport_mask[1];
+        w.m2 = q->fwd.lport_mask[2];
+        w.m3 = q->fwd.lport_mask[3];
+        w.acl_mode = q->fwd.acl_mode;
+        w.acl_swap = q->fwd.acl_flags & CNDP_ACL_F_MAC_SWAP;
+        if (q->conf.mode == CNDP_MQ_CFWD_FWD) {
+            hipLaunchKernelGGL(k_mq_cfwd<CNDP_CFWD_FWD>, dim3(g), dim3(MQ_TPB), 0, s, a, w, (const uint64_t *)nullptr,
+                               (const uint64_t *)nullptr);
+        } else if (q->conf.mode == CNDP_MQ_CFWD_L3FWD) {
+            // the FIB's mirror brought up to date on this stream, its view held until the launch
+            // is enqueued (as CNDP_MQ_IP4_LOOKUP does with the context's FIB)
+            struct cndp_tbl *t = &q->fwd.fib->t;
+            TblView v{};
+            if ((r = tbl_acquire(t, s, &v)))
+                return r;
+            if (!v.t24 || !v.t8) {
+                tbl_release(t);
+                return -EIO;
+            }
+            hipLaunchKernelGGL(k_mq_cfwd<CNDP_CFWD_L3FWD>, dim3(g), dim3(MQ_TPB), 0, s, a, w, (const uint64_t *)v.t24,
+                               (const uint64_t *)v.t8);
+            tbl_release(t);
+        } else {
+            // the ACL mirror's reader protocol: ordered after a reader on another stream, the
+            // image mirrored on this one, our end recorded for the next reader (acl_internal.h)
+            const uint32_t *img = nullptr;
+            if ((r = acl_dev_begin(q->fwd.acl, c->dev, s, &img, nullptr)))
+                return r; // -ENOENT: a failed build left no image
+            hipLaunchKernelGGL(k_mq_acl, dim3(g), dim3(MQ_TPB), 0, s, a, w, img);
+            const bool ok = hipGetLastError() == hipSuccess;
+            r = acl_dev_end(q->fwd.acl, s, ok);
+            if (!ok || r)
+                return ok ? r : -EIO;
+        }
     } else if (q->conf.mode == CNDP_MQ_IP4_REWRITE) {
         if ((r = rw_sync(c, s)))
             return r;
@@ -8261,12 +8582,16 @@ static void mq_fill(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k
             hmb[j] = i >= vec ? MQ_RW_TAIL : 0u;
             hlen[j] = *(const uint64_t *)(m + MB_UDATA64); // node_mbuf_priv1
         }
+        if (mode == CNDP_MQ_ACL_FWD)
+            hlen[j] = dlen; // validate_ipv4_pkt's link-length test
         if (zc) {
             if (!rw) {
                 const int km = mq_region(q, m, 64);
                 hmb[j] = km < 0 ? 0u : (uint64_t)(intptr_t)(m + q->rg[km].delta);
             }
-            if (cnet) {
+            if (mq_is_fwd(mode)) { // the kernels look at the frame word alone: none for an mbuf outside
+                hoff[j] = hmb[j] ? mq_frame_word(q, f) : 0u;
+            } else if (cnet) {
                 // frame offset in the batch's region (the first frame's);
                 // outside it: the region's end, which reads as zero bytes
                 const int kf = mq_region(q, f, 1);
@@ -8481,9 +8806,19 @@ static void mq_writeback(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
     }
     const uint8_t *R = sl->h + q->h_rec;
     const uint64_t *ho = (const uint64_t *)(sl->h + q->h_off);
-    if (mode == CNDP_MQ_MAC_SWAP || mode == CNDP_MQ_IP4_REWRITE) { // the changed bytes back into the frame
-        const uint32_t span = mode == CNDP_MQ_MAC_SWAP ? 12u : MQ_RW_STAGE;
+    if (mode == CNDP_MQ_MAC_SWAP || mode == CNDP_MQ_IP4_REWRITE || mq_is_fwd(mode)) { // the changed bytes back into the frame
+        // cndpfwd modes: fwd bytes 0-11, l3fwd up to byte 25, acl bytes 0-11 of the frames it
+        // forwarded (edge = a port) and only with the swap flag
+        const bool acl = mode == CNDP_MQ_ACL_FWD;
+        const uint32_t span = mode == CNDP_MQ_MAC_SWAP || mode == CNDP_MQ_CFWD_FWD ? 12u
+                            : mode == CNDP_MQ_CFWD_L3FWD                          ? 26u
+                            : acl ? ((q->fwd.acl_flags & CNDP_ACL_F_MAC_SWAP) ? 12u : 0u)
+                                  : MQ_RW_STAGE;
+        if (!span)
+            return;
         for (uint32_t i = i0; i < i1; i++) {
+            if (acl && ed[i] > 255u)
+                continue;
             uint8_t *m = (uint8_t *)sl->mb[i];
             uint8_t *buf = *(uint8_t **)(m + MB_BUF_ADDR);
             const uint16_t doff = *(const uint16_t *)(m + MB_DATA_OFF);
@@ -8529,6 +8864,24 @@ static void mq_writeback(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
                 mq_save_md_host(md, st + (doff - (uint16_t)(lens[i].y >> 16)),
                                 node == CNDP_MQ_NODE_IP6);
         }
+    }
+}
+
+// cndpfwd modes: the reference loops' counters by CNDP_MQ_STAT_* key, from the
+// edges of k mbufs (CNDP_MQ_EDGE_NONE counts nowhere)
+static void mq_count_fwd(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
+{
+    const bool acl = q->conf.mode == CNDP_MQ_ACL_FWD;
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t e = ed[i];
+        if (e == MQ_EDGE_NONE)
+            continue;
+        if (!acl)
+            q->n_fwd[(e & CNDP_MQ_EDGE_ECHO) ? CNDP_MQ_STAT_ECHO : CNDP_MQ_STAT_FORWARD]++;
+        else
+            q->n_fwd[e == CNDP_MQ_EDGE_ACL_PREFILTER ? CNDP_MQ_STAT_ACL_PREFILTER
+                     : e == CNDP_MQ_EDGE_ACL_DENY    ? CNDP_MQ_STAT_ACL_DENY
+                                                     : CNDP_MQ_STAT_ACL_PERMIT]++;
     }
 }
 
@@ -8580,6 +8933,8 @@ extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges,
             mq_writeback(q, sl, sl->polled, sl->polled + take);
         memcpy(mbufs + got, sl->mb + sl->polled, (size_t)take * sizeof(void *));
         memcpy(edges + got, (const uint16_t *)(sl->h + q->h_edge) + sl->polled, (size_t)take * 2);
+        if (mq_is_fwd(q->conf.mode)) // cndp_mqfwd.h: the counters, from the edges handed back
+            mq_count_fwd(q, edges + got, take);
         sl->polled += take;
         got += take;
         q->pending -= take;
@@ -8600,6 +8955,12 @@ extern "C" int64_t cndp_gpu_mq_stat(const cndp_gpu_mq_t *q, int key)
         return (int64_t)q->n_batches;
     case CNDP_MQ_STAT_MBUFS:
         return (int64_t)q->n_mbufs;
+    case CNDP_MQ_STAT_FORWARD: // cndp_mqfwd.h; a key of another mode's family stays 0
+    case CNDP_MQ_STAT_ECHO:
+    case CNDP_MQ_STAT_ACL_PREFILTER:
+    case CNDP_MQ_STAT_ACL_DENY:
+    case CNDP_MQ_STAT_ACL_PERMIT:
+        return (int64_t)q->n_fwd[key];
     default:
         return -EINVAL;
     }

@@ -111,10 +111,16 @@ class MbufQueue:
     METADATA_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p)
 
     def __init__(self, cl, mode: int, flags: int = 0, batch: int = 8192, depth: int = 4,
-                 max_delay_us: int = 50, umem=None, lport: int = 0, stage_max: int = 0, metadata=None):
+                 max_delay_us: int = 50, umem=None, lport: int = 0, stage_max: int = 0, metadata=None,
+                 fib=None, acl=None, acl_mode: int = N.CNDP_ACL_STRICT, acl_flags: int = 0, lports=()):
         """metadata: cnet's pktmbuf_metadata hook, a Python function of the mbuf
-        address returning the metadata address (None: m + 64)."""
+        address returning the metadata address (None: m + 64).
+        cndpfwd modes (CNDP_MQ_CFWD_FWD / _L3FWD / CNDP_MQ_ACL_FWD, cndp_mqfwd.h):
+        lport is the incoming port, lports the ports that exist, fib the l3fwd
+        FIB (cfwd.l3fwd_fib), acl an AclTable with acl_mode / acl_flags; the
+        FIB and the table must outlive the queue."""
         self._L = N.lib()
+        self._keep = (fib, acl)
         c = N.MqConf()
         c.mode, c.flags, c.batch, c.depth = mode, flags, batch, depth
         c.max_delay_us, c.stage_max, c.lport = max_delay_us, stage_max, lport
@@ -123,7 +129,19 @@ class MbufQueue:
         if self._md_fn:
             c.metadata = ctypes.cast(self._md_fn, ctypes.c_void_p)
         h = ctypes.c_void_p()
-        N.check(self._L.cndp_gpu_mq_create(cl.h, ctypes.byref(c), ctypes.byref(h)), "cndp_gpu_mq_create")
+        self.h = None
+        if mode in (N.CNDP_MQ_CFWD_FWD, N.CNDP_MQ_CFWD_L3FWD, N.CNDP_MQ_ACL_FWD):
+            from .acl import lport_mask
+            w = N.MqFwd()
+            w.fib = fib.h if fib is not None else None
+            w.acl = acl.h if acl is not None else None
+            w.acl_mode, w.acl_flags = acl_mode, acl_flags
+            for k, bits in enumerate(lport_mask(lports)):
+                w.lport_mask[k] = bits
+            N.check(self._L.cndp_gpu_mq_create_fwd(cl.h, ctypes.byref(c), ctypes.byref(w), ctypes.byref(h)),
+                    "cndp_gpu_mq_create_fwd")
+        else:
+            N.check(self._L.cndp_gpu_mq_create(cl.h, ctypes.byref(c), ctypes.byref(h)), "cndp_gpu_mq_create")
         self.h = h
         self.cl = cl
 
@@ -151,6 +169,10 @@ class MbufQueue:
     @property
     def pending(self) -> int:
         return self._L.cndp_gpu_mq_pending(self.h)
+
+    def stat(self, key: int) -> int:
+        """cndp_gpu_mq_stat: a CNDP_MQ_STAT_* counter."""
+        return N.check(self._L.cndp_gpu_mq_stat(self.h, key), "cndp_gpu_mq_stat")
 
     def poll(self, max_n: int = 1 << 16):
         out = (ctypes.c_void_p * max_n)()

@@ -1,7 +1,7 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
 include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h,
-include/cndp_acl.h and include/cndp_cfwd.h).
+include/cndp_acl.h, include/cndp_cfwd.h and include/cndp_mqfwd.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -140,6 +140,13 @@ CNDP_CFWD_PORT_MAX = 0x7FFF
 CNDP_CFWD_LPORT_NONE = 0xFFFF
 CNDP_CFWD_STAT_FORWARD, CNDP_CFWD_STAT_ECHO = range(2)
 CNDP_CFWD_NSTATS = 2
+# cndp_mqfwd.h
+CNDP_MQ_CFWD_FWD, CNDP_MQ_CFWD_L3FWD, CNDP_MQ_ACL_FWD = 4, 5, 6
+CNDP_MQ_EDGE_ECHO = 0x0100
+CNDP_MQ_EDGE_ACL_DENY = 0xFFFC
+CNDP_MQ_EDGE_ACL_PREFILTER = 0xFFFB
+(CNDP_MQ_STAT_FORWARD, CNDP_MQ_STAT_ECHO, CNDP_MQ_STAT_ACL_PREFILTER, CNDP_MQ_STAT_ACL_DENY,
+ CNDP_MQ_STAT_ACL_PERMIT) = range(3, 8)
 
 
 def CNDP_L4_EDGE(node: int, e: int) -> int:
@@ -189,6 +196,12 @@ class MqConf(Structure):
     _fields_ = [("mode", c_uint32), ("flags", c_uint32), ("batch", c_uint32), ("depth", c_uint32),
                 ("max_delay_us", c_uint32), ("stage_max", c_uint32), ("umem", c_void_p),
                 ("lport", c_uint16), ("rsvd", c_uint16 * 3), ("metadata", c_void_p)]
+
+
+class MqFwd(Structure):
+    """struct cndp_mq_fwd (cndp_mqfwd.h)."""
+    _fields_ = [("fib", c_void_p), ("acl", c_void_p), ("acl_mode", c_uint32), ("acl_flags", c_uint32),
+                ("lport_mask", c_uint64 * 4)]
 
 
 class PcbEntry(Structure):
@@ -373,6 +386,7 @@ def lib():
                                      c_uint32, c_void_p, c_void_p]),
         "cndp_gpu_set_tuning": (c_int, [c_void_p, c_int, c_int]),
         "cndp_gpu_mq_create": (c_int, [c_void_p, POINTER(MqConf), POINTER(c_void_p)]),
+        "cndp_gpu_mq_create_fwd": (c_int, [c_void_p, POINTER(MqConf), POINTER(MqFwd), POINTER(c_void_p)]),
         "cndp_gpu_mq_free": (None, [c_void_p]),
         "cndp_gpu_mq_submit": (c_int, [c_void_p, c_void_p, c_uint32]),
         "cndp_gpu_mq_flush": (c_int, [c_void_p]),
@@ -459,7 +473,7 @@ def exported_symbols():
     import re
     names = []
     inc = os.path.join(os.path.dirname(HERE), "include")
-    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h"):
+    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h"):
         with open(os.path.join(inc, h)) as f:
             txt = f.read()
         names += re.findall(r"^[A-Za-z_][\w \*]*?\b((?:cne|cndp|ip4)_\w+)\s*\(", txt, re.M)
