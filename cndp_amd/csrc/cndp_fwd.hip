@@ -16,6 +16,12 @@
 //           route and gateway lookups where the rule asks for them; the MACs.
 // Every frame read and write is bounded by slab_len; stores are plain vector
 // stores.  Counters go through LDS to one global atomic per block and counter.
+//
+// The object image's device mirror is one buffer, updated in place and guarded
+// by an event; the FIB mirrors are read through views.  Every reader --
+// cndp_gpu_ip4_forward here, the mbuf queue's CNDP_MQ_IP4_FORWARD kernel in
+// cndp_gpu.hip -- brackets its launch with fwd_dev_begin / fwd_dev_end
+// (fwd_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
@@ -39,9 +45,7 @@
 #define FWD_BLOCKS_PER_CU 8u
 
 // one FIB's device mirror: the /16 directory in front of tbl24 when it has one
-struct FibDev {
-    const uint32_t *t24, *t8, *d16, *pages;
-};
+typedef struct fwd_fibv FibDev;
 
 struct FwdArgs {
     uint8_t *slab;
@@ -433,14 +437,77 @@ static int fwd_launch(FwdDev *d, const FwdArgs &a, hipStream_t s)
     return 0;
 }
 
-static int fwd_run(FwdDev *d, struct cndp_fwd_tbl *t, const struct cndp_batch *b, uint32_t burst,
-                   const struct cndp_fwd_io *io, hipStream_t s)
+// fwd_dev_begin under t->lock: the device, the wait for a reader on another
+// stream, the image's mirror, both FIB mirrors synced and their views taken
+static int fwd_begin_locked(struct cndp_fwd_tbl *t, int dev, hipStream_t s, FwdDev **out, FibDev *arp, FibDev *rt)
 {
+    HIP_TRY(hipSetDevice(dev));
+    FwdDev *d = NULL;
+    int r = fwd_dev_get(t, dev, &d);
+    if (r)
+        return r;
     if (d->have_last && d->last != s)
         HIP_TRY(hipStreamWaitEvent(s, d->ev, 0));
-    int r = fwd_mirror(d, t, s);
-    if (r || b->n == 0)
+    if ((r = fwd_mirror(d, t, s)))
         return r;
+    struct cndp_tbl *ta = &t->arp_fib->t, *tr = &t->rt4_fib->t;
+    if ((r = fib_acquire(ta, s, arp)))
+        return r;
+    if ((r = fib_acquire(tr, s, rt))) {
+        fib_release(ta);
+        return r;
+    }
+    *out = d;
+    return 0;
+}
+
+// fwd_dev_end under t->lock: the views dropped, the reader's end recorded
+static int fwd_end_locked(struct cndp_fwd_tbl *t, hipStream_t s, int launched)
+{
+    FwdDev *d = (FwdDev *)t->dev;
+    fib_release(&t->rt4_fib->t);
+    fib_release(&t->arp_fib->t);
+    if (!launched)
+        return 0;
+    HIP_TRY(hipEventRecord(d->ev, s));
+    d->last = s;
+    d->have_last = 1;
+    return 0;
+}
+
+extern "C" int fwd_dev_begin(struct cndp_fwd_tbl *t, int dev, void *stream, const uint32_t **img,
+                             struct fwd_fibv *arp, struct fwd_fibv *rt)
+{
+    pthread_mutex_lock(&t->lock);
+    FwdDev *d = NULL;
+    const int r = fwd_begin_locked(t, dev, (hipStream_t)stream, &d, arp, rt);
+    if (r) {
+        pthread_mutex_unlock(&t->lock);
+        return r;
+    }
+    *img = d->img;
+    return 0;
+}
+
+extern "C" int fwd_dev_end(struct cndp_fwd_tbl *t, void *stream, int launched)
+{
+    const int r = fwd_end_locked(t, (hipStream_t)stream, launched);
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+extern "C" int fwd_dev_check(struct cndp_fwd_tbl *t, int dev)
+{
+    pthread_mutex_lock(&t->lock);
+    const FwdDev *d = (const FwdDev *)t->dev;
+    const int r = d && d->dev != dev ? -EINVAL : 0; // one table, one device
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+static int fwd_run(FwdDev *d, const struct cndp_batch *b, uint32_t burst, const struct cndp_fwd_io *io,
+                   const FibDev &arp, const FibDev &rt, hipStream_t s)
+{
     FwdArgs a;
     a.slab = (uint8_t *)b->slab;
     a.slab_len = b->slab_len;
@@ -458,26 +525,12 @@ static int fwd_run(FwdDev *d, struct cndp_fwd_tbl *t, const struct cndp_batch *b
     a.n_bins = io->n_bins;
     a.stats = (unsigned long long *)io->stats;
     a.img = d->img;
+    a.arp = arp;
+    a.rt = rt;
     a.burst = burst;
     a.per = FWD_BLOCK / burst * burst;
     a.tiles = ((uint64_t)b->n + a.per - 1u) / a.per;
-
-    struct cndp_tbl *ta = &t->arp_fib->t, *tr = &t->rt4_fib->t;
-    r = fib_acquire(ta, s, &a.arp);
-    if (r)
-        return r;
-    r = fib_acquire(tr, s, &a.rt);
-    if (!r) {
-        r = fwd_launch(d, a, s);
-        fib_release(tr);
-    }
-    fib_release(ta);
-    if (r)
-        return r;
-    HIP_TRY(hipEventRecord(d->ev, s));
-    d->last = s;
-    d->have_last = 1;
-    return 0;
+    return fwd_launch(d, a, s);
 }
 
 extern "C" int cndp_gpu_ip4_forward(cndp_gpu_ctx_t *ctx, cndp_fwd_tbl_t *tbl, const struct cndp_batch *b,
@@ -494,10 +547,15 @@ extern "C" int cndp_gpu_ip4_forward(cndp_gpu_ctx_t *ctx, cndp_fwd_tbl_t *tbl, co
     if (io->bin_of && ((int64_t)io->n_bins <= (int64_t)fwd_max_netif(tbl) || io->n_bins > 65533u))
         r = -EINVAL;
     FwdDev *d = NULL;
+    FibDev arp, rt;
     if (!r)
-        r = fwd_dev_get(tbl, dev, &d);
-    if (!r)
-        r = fwd_run(d, tbl, b, burst, io, (hipStream_t)stream);
+        r = fwd_begin_locked(tbl, dev, (hipStream_t)stream, &d, &arp, &rt);
+    if (!r) {
+        if (b->n)
+            r = fwd_run(d, b, burst, io, arp, rt, (hipStream_t)stream);
+        const int e = fwd_end_locked(tbl, (hipStream_t)stream, b->n && !r);
+        r = r ? r : e;
+    }
     pthread_mutex_unlock(&tbl->lock);
     return r;
 }

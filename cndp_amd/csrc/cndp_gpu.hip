@@ -35,6 +35,8 @@
 #include "acl_internal.h"           // the cndpfwd queue modes' per-frame rules
 #include "cfwd_internal.h"
 #include "../../include/cndp_mqfwd.h"
+#include "fwd_internal.h"           // the ip4_forward queue mode's group rule and its table's reader protocol
+#include "../../include/cndp_mqcnet.h"
 
 #define CNDP_VERSION "cndp_amd 0.1 (gfx950)"
 
@@ -7653,6 +7655,139 @@ __global__ __launch_bounds__(MQ_TPB) void k_mq_acl(MqArgs a, MqFwd w, const uint
     mq_complete(a);
 }
 
+// cnet's ip4_forward node (cndp_mqcnet.h, ip4_forward.c:50-335).  A block is
+// one wave and owns one chunk of at most 64 consecutive mbufs of ONE submitted
+// burst: the host's chunk table gives its first mbuf and its count, chunks
+// start at multiples of 64 inside their burst, so the reference's groups of
+// four are lane quads of the wave and the last chunk's count & ~3 is where the
+// burst's 1-wide tail begins.  The rule is fwd_rule_direct / _route / _finish
+// (fwd_internal.h), the text cndp_fwd_node_host runs; a group's hit flags
+// travel by a ballot and lane 0's gateway entry by a shuffle -- no LDS, no
+// barrier.  All lanes of the wave run all three steps (a lane past the count
+// or without a frame hits nothing), so the cross-lane operations are never
+// divergent.
+//   zero-copy  a.off[i] is the frame word of the IPv4 header (mtod at submit),
+//              a.priv[i] = l2_len | MQ_IPF_ADJ when l2_len <= data_off |
+//              back << 8, the bytes in front of the header that lie in its
+//              region (at most l2_len).  Header bytes 8-11 and 16-19 are read,
+//              byte 8, bytes 10-11 and the 12 MAC bytes at header - l2_len
+//              stored, each bounded; a header byte the MAC bytes cover
+//              (l2_len < 12) takes the MAC's value and is stored once.
+//   staged     the slot's staging holds header bytes 8-19 at +0; the new bytes
+//              8-11 go back to +0 and the MAC bytes to +16; poll copies them
+//              into the frame in the reference's order.
+// The mbuf header is never written here: poll adjusts data_off / data_len.
+#define MQ_IPF_STAGE 32u
+#define MQ_IPF_ADJ 0x80u
+#define MQ_IPF_CNT_SHIFT 24u // chunk word: first mbuf | count << 24
+
+struct MqIpf {
+    const uint32_t *img;     // the table's object image (device mirror)
+    struct fwd_fibv arp, rt; // views of the two FIB mirrors
+    const uint32_t *chunk;
+    uint32_t nch;
+};
+
+__global__ __launch_bounds__(MQ_TPB) void k_mq_ip4_forward(MqArgs a, MqIpf w)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t q0 = lane & ~3u; // the quad's lane 0
+    for (uint32_t c = blockIdx.x; c < w.nch; c += gridDim.x) {
+        const uint32_t cw = w.chunk[c], i0 = cw & ((1u << MQ_IPF_CNT_SHIFT) - 1u);
+        uint32_t cnt = cw >> MQ_IPF_CNT_SHIFT;
+        if (cnt > MQ_TPB || i0 + cnt > a.n) // never from mq_fill; no access past the batch's arrays
+            cnt = 0;
+        const bool live = lane < cnt;
+        const bool quad = lane < (cnt & ~3u); // the 4-wide loop; else the 1-wide loop
+        const uint32_t i = i0 + lane;
+        uint8_t *p = nullptr;
+        uint32_t avail = 0, pv = 0;
+        if (live) {
+            pv = (uint32_t)a.priv[i];
+            if (a.zc) {
+                p = mq_frame(a.off[i], avail);
+            } else {
+                p = (uint8_t *)a.slab + a.off[i];
+                avail = MQ_IPF_STAGE;
+            }
+        }
+        const bool taken = p != nullptr;
+        uint32_t w0 = 0, dst = 0;
+        if (taken) {
+            if (!a.zc) {
+                w0 = ((const uint32_t *)p)[0];
+                dst = ((const uint32_t *)p)[2];
+            } else if ((((uintptr_t)p) & 3u) == 0 && avail >= 20u) {
+                w0 = ((const uint32_t *)p)[2];
+                dst = ((const uint32_t *)p)[4];
+            } else {
+                w0 = mqf_le32(p, avail, 8);
+                dst = mqf_le32(p, avail, 16);
+            }
+        }
+        struct fwd_member m;
+        fwd_rule_direct(w.img, &w.arp, dst, taken, &m);
+        const unsigned long long hits = __ballot(m.a_hit != 0u);
+        const uint32_t group_hit = quad ? (uint32_t)((hits >> q0) & 0xFull) : m.a_hit;
+        fwd_rule_route(w.img, &w.arp, &w.rt, taken, group_hit, &m);
+        const uint32_t gw0 = __shfl(m.g_hit ? m.g_idx : CNDP_FWD_NONE, (int)q0, 64);
+        if (!live)
+            continue;
+        if (!taken) {
+            a.edges[i] = (uint16_t)MQ_EDGE_NONE;
+            continue;
+        }
+        struct fwd_answer o;
+        fwd_rule_finish(w.img, &m, quad && lane != q0, gw0, &o);
+        uint32_t ttl, ck;
+        fwd_adjust_cksum(w0, &ttl, &ck);
+        if (!a.zc) {
+            uint32_t *d = (uint32_t *)p;
+            d[0] = (w0 & 0x0000FF00u) | ttl | ck << 16;
+            if (o.ha != CNDP_FWD_NONE) {
+                d[4] = o.d0;
+                d[5] = o.d1;
+                d[6] = o.d2;
+            }
+        } else {
+            const uint32_t l2 = pv & 0x7Fu, back = (pv >> 8) & 0x7Fu;
+            const bool mac = o.ha != CNDP_FWD_NONE && (pv & MQ_IPF_ADJ);
+            // header byte j is MAC byte l2 + j: covered ones are left to the MAC stores
+            if (!(mac && l2 + 8u < 12u))
+                mqf_store<1>(p, avail, 8, ttl);
+            if (!(mac && l2 + 11u < 12u)) { // l2 >= 1: byte 11 is the header's; byte 10 too unless l2 == 1
+                if (!(mac && l2 + 10u < 12u)) {
+                    if ((((uintptr_t)p) & 1u) == 0 && avail >= 12u)
+                        *(uint16_t *)(p + 10) = (uint16_t)ck;
+                    else
+                        mqf_store<2>(p, avail, 10, ck);
+                } else {
+                    mqf_store<1>(p, avail, 11, ck >> 8);
+                }
+            }
+            if (mac) {
+                // MAC byte k lies at p - l2 + k: writable from p - back up to p + avail
+                uint8_t *e = p - l2;
+                const uint32_t lo = l2 - back, hi = l2 + avail; // back <= l2, so no wrap
+                if (lo == 0 && hi >= 12u && (((uintptr_t)e) & 3u) == 0) {
+                    uint32_t *d = (uint32_t *)e;
+                    d[0] = o.d0;
+                    d[1] = o.d1;
+                    d[2] = o.d2;
+                } else {
+                    const uint32_t dw[3] = {o.d0, o.d1, o.d2};
+#pragma unroll
+                    for (uint32_t k = 0; k < 12u; k++)
+                        if (k >= lo && k < hi)
+                            e[k] = (uint8_t)(dw[k >> 2] >> (8u * (k & 3u)));
+                }
+            }
+        }
+        a.edges[i] = (uint16_t)o.edge;
+    }
+    mq_complete(a);
+}
+
 // ip4_rewrite_node_process (ip4_rewrite.c:40-247) per packet of the node's
 // bursts: the next hop's rewrite data at mtod (:85), TTL = priv1.ttl - 1 and
 // the checksum from priv1.cksum + htons(0x0100) -- in the 4-wide loop with
@@ -7946,7 +8081,8 @@ struct MqSlot {
     uint32_t nrun;         // cnet: runs of equal-size bursts (each ends with at most one short burst)
     uint32_t run_B[MQ_RUNS_MAX], run_n[MQ_RUNS_MAX];
     uint8_t run_closed;
-    uint32_t nb;           // CNDP_MQ_F_REWRITE: submitted bursts (their starts at h_bst)
+    uint32_t nb;           // CNDP_MQ_F_REWRITE: submitted bursts (their starts at h_bst);
+                           // CNDP_MQ_IP4_FORWARD: chunks of at most 64 mbufs of one burst (their words at h_bst)
     void **mb;             // host
     uint8_t *h, *hd;       // pinned + mapped block (host view, device view)
     uint8_t *d;            // device block (cnet classify outputs)
@@ -7983,6 +8119,8 @@ struct cndp_gpu_mq {
     uint64_t n_batches, n_mbufs;   // launched so far (cndp_gpu_mq_stat)
     struct cndp_mq_fwd fwd;        // cndpfwd modes (cndp_gpu_mq_create_fwd): the tables and the known ports
     uint64_t n_fwd[CNDP_MQ_STAT_ACL_PERMIT + 1]; // their counters by CNDP_MQ_STAT_* key, counted by poll
+    cndp_fwd_tbl_t *ipf;           // CNDP_MQ_IP4_FORWARD (cndp_gpu_mq_create_ip4_forward): the forwarding table
+    uint64_t n_ipf[3];             // its counters, CNDP_MQ_STAT_FWD_DIRECT + k, counted by poll
     MqSlot slot[CNDP_MQ_DEPTH_MAX];
 };
 
@@ -8025,17 +8163,19 @@ static inline bool mq_is_fwd(uint32_t mode)
     return mode == CNDP_MQ_CFWD_FWD || mode == CNDP_MQ_CFWD_L3FWD || mode == CNDP_MQ_ACL_FWD;
 }
 
-// fwd: the tables of a cndpfwd mode, checked by cndp_gpu_mq_create_fwd; nullptr for the node modes
+// fwd: the tables of a cndpfwd mode, checked by cndp_gpu_mq_create_fwd; ipf: the forwarding table of
+// CNDP_MQ_IP4_FORWARD, checked by cndp_gpu_mq_create_ip4_forward; both nullptr for the node modes
 static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const struct cndp_mq_fwd *fwd,
-                     cndp_gpu_mq_t **out)
+                     cndp_fwd_tbl_t *ipf, cndp_gpu_mq_t **out)
 {
     if (!c || !conf || !out)
         return -EINVAL;
     *out = nullptr;
     struct cndp_mq_conf k = *conf;
-    if (fwd ? !mq_is_fwd(k.mode)
-            : (k.mode != CNDP_MQ_IP4_LOOKUP && k.mode != CNDP_MQ_CNET && k.mode != CNDP_MQ_MAC_SWAP &&
-               k.mode != CNDP_MQ_IP4_REWRITE))
+    if (ipf ? k.mode != CNDP_MQ_IP4_FORWARD
+        : fwd ? !mq_is_fwd(k.mode)
+              : (k.mode != CNDP_MQ_IP4_LOOKUP && k.mode != CNDP_MQ_CNET && k.mode != CNDP_MQ_MAC_SWAP &&
+                 k.mode != CNDP_MQ_IP4_REWRITE))
         return -EINVAL;
     if (k.flags & ~(CNDP_MQ_F_HASH | CNDP_MQ_F_NO_METADATA | CNDP_MQ_F_DEVICE_HEADERS | CNDP_MQ_F_RX_PARSE |
                     CNDP_MQ_F_REWRITE | CNDP_MQ_F_HOST_WRITEBACK))
@@ -8070,6 +8210,7 @@ static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const s
     q->conf = k;
     if (fwd)
         q->fwd = *fwd;
+    q->ipf = ipf;
     if (k.umem) {
         // zero-copy: every region the context holds (the UMEMs of all the
         // graph's ports), conf.umem among them
@@ -8089,24 +8230,26 @@ static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const s
     }
     const uint64_t B = k.batch;
     const bool cnet = k.mode == CNDP_MQ_CNET, rw = k.mode == CNDP_MQ_IP4_REWRITE;
-    const bool acl = k.mode == CNDP_MQ_ACL_FWD, cfwd = mq_is_fwd(k.mode);
+    const bool acl = k.mode == CNDP_MQ_ACL_FWD, cfwd = mq_is_fwd(k.mode), fw4 = k.mode == CNDP_MQ_IP4_FORWARD;
     const bool zc = q->zc != 0;
     q->stage = zc ? 0u
              : cnet ? (uint32_t)al64(k.stage_max)
              : k.mode == CNDP_MQ_IP4_LOOKUP ? ((k.flags & CNDP_MQ_F_RX_PARSE) ? 32u : MQ_W4)
              : k.mode == CNDP_MQ_MAC_SWAP || k.mode == CNDP_MQ_CFWD_FWD ? MQ_SWAP
-             : cfwd ? MQ_FWD_STAGE : MQ_RW_STAGE;
+             : cfwd ? MQ_FWD_STAGE
+             : fw4 ? MQ_IPF_STAGE : MQ_RW_STAGE;
     q->h_mb = 0;                                          // zc: mbuf device addresses; rewrite: tail flags
     q->h_off = al64(B * 8);                               // frame words / offsets
-    q->h_len = q->h_off + al64(B * 8);                    // cnet: length fields; rewrite: priv1; acl: data_len
-    q->h_md = q->h_len + (cnet || rw || acl ? al64(B * 8) : 0); // cnet zc: metadata addresses
+    q->h_len = q->h_off + al64(B * 8);                    // cnet: length fields; rewrite: priv1; acl: data_len;
+                                                          // ip4_forward: l2_len | MQ_IPF_ADJ | back << 8
+    q->h_md = q->h_len + (cnet || rw || acl || fw4 ? al64(B * 8) : 0); // cnet zc: metadata addresses
     q->h_edge = q->h_md + (cnet && zc ? al64(B * 8) : 0);
     q->hostwb = zc && (k.flags & CNDP_MQ_F_HOST_WRITEBACK);
     q->h_rec = q->h_edge + al64(B * 2);                   // staged (and host writeback): records
-    q->h_rmd = q->h_rec + ((zc && !q->hostwb) || rw || cfwd || k.mode == CNDP_MQ_MAC_SWAP ? 0 : al64(B * (cnet ? 16 : 8)));
+    q->h_rmd = q->h_rec + ((zc && !q->hostwb) || rw || cfwd || fw4 || k.mode == CNDP_MQ_MAC_SWAP ? 0 : al64(B * (cnet ? 16 : 8)));
     q->h_stage = q->h_rmd + (q->hostwb && cnet ? B * 32 : 0); // cnet host writeback: metadata addresses
-    q->h_bst = q->h_stage + B * q->stage;                 // CNDP_MQ_F_REWRITE: burst starts
-    q->h_bytes = q->h_bst + ((k.flags & CNDP_MQ_F_REWRITE) ? al64((B + 1) * 4) : 0);
+    q->h_bst = q->h_stage + B * q->stage;                 // CNDP_MQ_F_REWRITE: burst starts; ip4_forward: chunk words
+    q->h_bytes = q->h_bst + ((k.flags & CNDP_MQ_F_REWRITE) || fw4 ? al64((B + 1) * 4) : 0);
     q->d_nh = 0;
     q->d_edge = q->d_nh + al64(B * 4);
     q->d_pt = q->d_edge + al64(B);
@@ -8149,7 +8292,7 @@ fail:
 
 extern "C" int cndp_gpu_mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, cndp_gpu_mq_t **out)
 {
-    return mq_create(c, conf, nullptr, out);
+    return mq_create(c, conf, nullptr, nullptr, out);
 }
 
 // cndp_mqfwd.h: the argument rules of the three cndpfwd modes, then the queue as for every mode
@@ -8184,7 +8327,22 @@ extern "C" int cndp_gpu_mq_create_fwd(cndp_gpu_ctx_t *c, const struct cndp_mq_co
         if (!built)
             return -ENOENT;
     }
-    return mq_create(c, conf, fwd, out);
+    return mq_create(c, conf, fwd, nullptr, out);
+}
+
+// cndp_mqcnet.h: cnet's ip4_forward node over a forwarding table
+extern "C" int cndp_gpu_mq_create_ip4_forward(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf,
+                                              cndp_fwd_tbl_t *tbl, cndp_gpu_mq_t **out)
+{
+    if (!c || !conf || !tbl || !out)
+        return -EINVAL;
+    *out = nullptr;
+    if (conf->mode != CNDP_MQ_IP4_FORWARD || conf->flags)
+        return -EINVAL;
+    const int r = fwd_dev_check(tbl, c->dev); // one table, one device, as cndp_gpu_ip4_forward has it
+    if (r)
+        return r;
+    return mq_create(c, conf, nullptr, tbl, out);
 }
 
 extern "C" void cndp_gpu_mq_free(cndp_gpu_mq_t *q)
@@ -8337,6 +8495,20 @@ static int mq_launch_kernels(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t slot_i)
             if (!ok || r)
                 return ok ? r : -EIO;
         }
+    } else if (q->conf.mode == CNDP_MQ_IP4_FORWARD) {
+        // the table's reader protocol (fwd_internal.h): ordered after a reader on another stream,
+        // the image and both FIBs mirrored on this one, the views held until the launch is enqueued
+        MqIpf w;
+        memset(&w, 0, sizeof(w));
+        if ((r = fwd_dev_begin(q->ipf, c->dev, s, &w.img, &w.arp, &w.rt)))
+            return r;
+        w.chunk = (const uint32_t *)(HD + q->h_bst);
+        w.nch = sl->nb;
+        hipLaunchKernelGGL(k_mq_ip4_forward, dim3(sl->nb < 65536u ? sl->nb : 65536u), dim3(MQ_TPB), 0, s, a, w);
+        const bool ok = hipGetLastError() == hipSuccess;
+        r = fwd_dev_end(q->ipf, s, ok);
+        if (!ok || r)
+            return ok ? r : -EIO;
     } else if (q->conf.mode == CNDP_MQ_IP4_REWRITE) {
         if ((r = rw_sync(c, s)))
             return r;
@@ -8526,6 +8698,7 @@ static void mq_fill(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k
 {
     const uint32_t mode = q->conf.mode;
     const bool cnet = mode == CNDP_MQ_CNET, rw = mode == CNDP_MQ_IP4_REWRITE, zc = q->zc != 0;
+    const bool fw4 = mode == CNDP_MQ_IP4_FORWARD;
     const bool want_md = cnet && zc && !(q->conf.flags & CNDP_MQ_F_NO_METADATA);
     const bool devhdr = q->devhdr != 0;
     uint8_t *H = sl->h;
@@ -8584,6 +8757,11 @@ static void mq_fill(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k
         }
         if (mode == CNDP_MQ_ACL_FWD)
             hlen[j] = dlen; // validate_ipv4_pkt's link-length test
+        uint32_t l2 = 0;
+        if (fw4) { // m->l2_len, and whether pktmbuf_adjust(m, -l2_len) takes place (l2_len <= data_off)
+            l2 = (uint32_t)(*(const uint64_t *)(m + MB_TX_OFFLOAD) & 0x7Fu);
+            hlen[j] = l2 | (l2 <= doff ? MQ_IPF_ADJ : 0u);
+        }
         if (zc) {
             if (!rw) {
                 const int km = mq_region(q, m, 64);
@@ -8591,6 +8769,14 @@ static void mq_fill(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k
             }
             if (mq_is_fwd(mode)) { // the kernels look at the frame word alone: none for an mbuf outside
                 hoff[j] = hmb[j] ? mq_frame_word(q, f) : 0u;
+            } else if (fw4) {
+                // the frame word of the IPv4 header, and how many of the l2_len bytes in front of
+                // it lie in its region (rg_last after mq_frame_word): the MAC bytes go there
+                hoff[j] = hmb[j] ? mq_frame_word(q, f) : 0u;
+                if (hoff[j]) {
+                    const uint64_t in_front = (uint64_t)(f - q->rg[q->rg_last].host);
+                    hlen[j] |= (uint64_t)(in_front < l2 ? (uint32_t)in_front : l2) << 8;
+                }
             } else if (cnet) {
                 // frame offset in the batch's region (the first frame's);
                 // outside it: the region's end, which reads as zero bytes
@@ -8618,13 +8804,16 @@ static void mq_fill(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k
                 const bool rxp = (q->conf.flags & CNDP_MQ_F_RX_PARSE) != 0;
                 at = rxp ? MQ_W4R_AT : MQ_W4_AT;
                 want = rxp ? MQ_W4R : MQ_W4;
+            } else if (fw4) { // header bytes 8-19: TTL, checksum, destination
+                at = 8;
+                want = 12;
             } else {
                 want = q->stage;
             }
             const uint32_t cp = room > at ? (room - at < want ? room - at : want) : 0u;
             uint8_t *dst = H + q->h_stage + sl->stage_used;
             memcpy(dst, f + at, cp);
-            const uint64_t span = cnet ? al64(want ? want : 1) : (uint64_t)((want + 15u) & ~15u);
+            const uint64_t span = cnet ? al64(want ? want : 1) : fw4 ? (uint64_t)MQ_IPF_STAGE : (uint64_t)((want + 15u) & ~15u);
             memset(dst + cp, 0, span - cp);
             hoff[j] = sl->stage_used;
             sl->stage_used += span;
@@ -8670,6 +8859,10 @@ extern "C" int cndp_gpu_mq_submit(cndp_gpu_mq_t *q, void *const *mbufs, uint32_t
         }
         if (q->conf.flags & CNDP_MQ_F_REWRITE) // this burst's first mbuf (the kernel's block)
             ((uint32_t *)(sl->h + q->h_bst))[sl->nb++] = sl->n;
+        if (q->conf.mode == CNDP_MQ_IP4_FORWARD) // this burst's chunks of 64 (k_mq_ip4_forward's waves)
+            for (uint32_t c0 = 0; c0 < k; c0 += MQ_TPB)
+                ((uint32_t *)(sl->h + q->h_bst))[sl->nb++] =
+                    (sl->n + c0) | ((k - c0 < MQ_TPB ? k - c0 : MQ_TPB) << MQ_IPF_CNT_SHIFT);
         mq_fill(q, sl, mbufs + done, k);
         if (cnet) { // runs of equal-size bursts, each closed by a shorter one
             if (sl->nrun && !sl->run_closed && k == sl->run_B[sl->nrun - 1]) {
@@ -8716,6 +8909,43 @@ static void mq_writeback(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
 {
     const uint32_t mode = q->conf.mode;
     const uint16_t *ed = (const uint16_t *)(sl->h + q->h_edge);
+    if (mode == CNDP_MQ_IP4_FORWARD) {
+        // pktmbuf_adjust(m, -l2_len) on the host, zero-copy or staged; staged also the frame
+        // bytes, in the reference's order: TTL / checksum at the old mtod, then the MAC bytes at
+        // the new one (which win where l2_len < 12 makes them overlap), each below buf_len
+        const uint64_t *hl = (const uint64_t *)(sl->h + q->h_len), *ho = (const uint64_t *)(sl->h + q->h_off);
+        for (uint32_t i = i0; i < i1; i++) {
+            if (i + MQ_PF < i1)
+                __builtin_prefetch(sl->mb[i + MQ_PF], 1);
+            if (ed[i] == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
+                continue;
+            uint8_t *m = (uint8_t *)sl->mb[i];
+            const uint16_t doff = *(const uint16_t *)(m + MB_DATA_OFF);
+            const uint16_t l2 = (uint16_t)(hl[i] & 0x7Fu);
+            const bool adj = (hl[i] & MQ_IPF_ADJ) != 0;
+            if (!q->zc) {
+                uint8_t *buf = *(uint8_t **)(m + MB_BUF_ADDR);
+                const uint16_t blen = *(const uint16_t *)(m + MB_BUF_LEN);
+                const uint8_t *st = sl->h + q->h_stage + ho[i];
+                if ((uint32_t)doff + 8u < blen)
+                    buf[doff + 8u] = st[0];
+                for (uint32_t j = 10; j < 12; j++)
+                    if ((uint32_t)doff + j < blen)
+                        buf[doff + j] = st[j - 8u];
+                if (adj && (ed[i] & CNDP_MQ_EDGE_FWD_MASK) != CNDP_FWD_EDGE_ARP_REQUEST) {
+                    const uint32_t e0 = (uint32_t)doff - l2;
+                    for (uint32_t j = 0; j < 12; j++)
+                        if (e0 + j < blen)
+                            buf[e0 + j] = st[16u + j];
+                }
+            }
+            if (adj) {
+                *(uint16_t *)(m + MB_DATA_OFF) = (uint16_t)(doff - l2);
+                *(uint16_t *)(m + MB_DATA_LEN) = (uint16_t)(*(const uint16_t *)(m + MB_DATA_LEN) + l2);
+            }
+        }
+        return;
+    }
     if (mode == CNDP_MQ_IP4_LOOKUP && (q->hostwb || !q->zc)) {
         // node_mbuf_priv1 (ip4_lookup.c:144-154) and, with the soft parse,
         // packet_type: staged from the staged ethertype, host writeback from
@@ -8885,6 +9115,20 @@ static void mq_count_fwd(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
     }
 }
 
+// ip4_forward mode: the node's three outcomes from the edges of k mbufs
+// (CNDP_MQ_EDGE_NONE counts nowhere)
+static void mq_count_ipf(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
+{
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t e = ed[i];
+        if (e == MQ_EDGE_NONE)
+            continue;
+        q->n_ipf[(e & CNDP_MQ_EDGE_FWD_GATEWAY)                                 ? CNDP_FWD_STAT_GATEWAY
+                 : (e & CNDP_MQ_EDGE_FWD_MASK) == CNDP_FWD_EDGE_ARP_REQUEST ? CNDP_FWD_STAT_ARP_REQUEST
+                                                                            : CNDP_FWD_STAT_DIRECT]++;
+    }
+}
+
 extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, uint32_t max)
 {
     if (!q || (max && (!mbufs || !edges)))
@@ -8935,6 +9179,8 @@ extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges,
         memcpy(edges + got, (const uint16_t *)(sl->h + q->h_edge) + sl->polled, (size_t)take * 2);
         if (mq_is_fwd(q->conf.mode)) // cndp_mqfwd.h: the counters, from the edges handed back
             mq_count_fwd(q, edges + got, take);
+        if (q->conf.mode == CNDP_MQ_IP4_FORWARD) // cndp_mqcnet.h
+            mq_count_ipf(q, edges + got, take);
         sl->polled += take;
         got += take;
         q->pending -= take;
@@ -8961,6 +9207,12 @@ extern "C" int64_t cndp_gpu_mq_stat(const cndp_gpu_mq_t *q, int key)
     case CNDP_MQ_STAT_ACL_DENY:
     case CNDP_MQ_STAT_ACL_PERMIT:
         return (int64_t)q->n_fwd[key];
+    case CNDP_MQ_STAT_FWD_DIRECT: // cndp_mqcnet.h
+        return (int64_t)q->n_ipf[CNDP_FWD_STAT_DIRECT];
+    case CNDP_MQ_STAT_FWD_GATEWAY:
+        return (int64_t)q->n_ipf[CNDP_FWD_STAT_GATEWAY];
+    case CNDP_MQ_STAT_FWD_ARP_REQUEST:
+        return (int64_t)q->n_ipf[CNDP_FWD_STAT_ARP_REQUEST];
     default:
         return -EINVAL;
     }

@@ -1,14 +1,16 @@
 /*
  * fwd.c -- the forwarding table of include/cndp_fwd.h: what ip4_forward reads of
  * this_cnet (the ARP and route FIBs, the object arrays fib_info_lookup indexes,
- * the netif MACs), the node's 1-wide rule on the host (ip4_forward.c:271-318)
+ * the netif MACs), the node's 1-wide rule on the host (ip4_forward.c:271-318),
+ * the whole node over one burst of mbufs (cndp_fwd_node_host, cndp_mqcnet.h)
  * and the object image the device stage mirrors.  Plain C, no HIP: it also
- * builds into a stand-alone program (tests/fwd_host).
+ * builds into stand-alone programs (tests/fwd_host, tests/mq_ip4fwd_host).
  */
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/cndp_mqcnet.h"
 #include "fwd_internal.h"
 
 static int fib_ok(const struct cne_fib *f)
@@ -240,6 +242,124 @@ int cndp_fwd_lookup(cndp_fwd_tbl_t *t, const uint32_t *dst_be, uint32_t n, struc
             if (r && (a = arp_obj(t, r[0])) != NULL) /* the gateway's s_addr as it is stored */
                 fill(t, o, r[1] & 0xffu, a);
         }
+    }
+    if (f1 != f0)
+        pthread_mutex_unlock(&f1->t.dev_lock);
+    pthread_mutex_unlock(&f0->t.dev_lock);
+    pthread_mutex_unlock(&t->lock);
+    return 0;
+}
+
+/* ---- the node over mbufs on the calling thread (include/cndp_mqcnet.h) ---- */
+/* pktmbuf_t fields (pktmbuf.h:102-204) */
+#define NB_BUF_ADDR 8
+#define NB_DATA_OFF 24
+#define NB_BUF_LEN 28
+#define NB_DATA_LEN 30
+#define NB_TX_OFFLOAD 40
+
+_Static_assert(FWD_EDGE_GATEWAY == CNDP_MQ_EDGE_FWD_GATEWAY, "the rule's gateway bit is the header's");
+
+static inline uint16_t ld16(const uint8_t *p)
+{
+    uint16_t v;
+    memcpy(&v, p, 2);
+    return v;
+}
+
+/* one member of a group between the node's head (:112-115) and its MAC writes */
+struct node_mb {
+    uint8_t *m;      /* NULL: not taken */
+    uintptr_t f;     /* pktmbuf_mtod at entry: the IPv4 header */
+    uintptr_t lim;   /* the first address that is not readable */
+    uint32_t l2, adj; /* l2_len; pktmbuf_adjust took place */
+    uint32_t dst;
+};
+
+/* hdr->dst_addr, ipv4_adjust_cksum, pktmbuf_adjust(m, -l2_len) */
+static void node_head(void *mbuf, const void *readable_end, struct node_mb *x)
+{
+    uint8_t *m = (uint8_t *)mbuf;
+    const uintptr_t end = (uintptr_t)readable_end;
+    memset(x, 0, sizeof(*x));
+    if (!m || (end && (uintptr_t)m + 64u > end))
+        return;
+    uint64_t buf, txo;
+    memcpy(&buf, m + NB_BUF_ADDR, 8);
+    memcpy(&txo, m + NB_TX_OFFLOAD, 8);
+    const uint16_t doff = ld16(m + NB_DATA_OFF), blen = ld16(m + NB_BUF_LEN), dlen = ld16(m + NB_DATA_LEN);
+    x->f = (uintptr_t)buf + doff;
+    x->lim = end ? end : (uintptr_t)buf + blen;
+    if (end && x->f >= end)
+        return; /* the frame lies outside the region */
+    x->m = m;
+    x->l2 = (uint32_t)(txo & 0x7Fu);
+    uint32_t w[3] = {0, 0, 0};
+    for (uint32_t j = 0; j < 12; j++)
+        if (x->f + 8u + j < x->lim)
+            w[j >> 2] |= (uint32_t)*(const uint8_t *)(x->f + 8u + j) << (8u * (j & 3u));
+    x->dst = w[2];
+    uint32_t ttl, ck;
+    fwd_adjust_cksum(w[0], &ttl, &ck);
+    if (x->f + 8u < x->lim)
+        *(uint8_t *)(x->f + 8u) = (uint8_t)ttl;
+    if (x->f + 10u < x->lim)
+        *(uint8_t *)(x->f + 10u) = (uint8_t)ck;
+    if (x->f + 11u < x->lim)
+        *(uint8_t *)(x->f + 11u) = (uint8_t)(ck >> 8);
+    x->adj = x->l2 <= doff; /* else pktmbuf_adj_offset answers NULL: the header fields stay */
+    if (x->adj) {
+        const uint16_t noff = (uint16_t)(doff - x->l2), nlen = (uint16_t)(dlen + x->l2);
+        memcpy(m + NB_DATA_OFF, &noff, 2);
+        memcpy(m + NB_DATA_LEN, &nlen, 2);
+    }
+}
+
+int cndp_fwd_node_host(cndp_fwd_tbl_t *t, void *const *mbufs, uint32_t n, uint16_t *edges, const void *readable_end)
+{
+    if (!t || n > 256u || (n && (!mbufs || !edges)))
+        return -EINVAL;
+    pthread_mutex_lock(&t->lock);
+    struct cne_fib *f0 = t->arp_fib < t->rt4_fib ? t->arp_fib : t->rt4_fib;
+    struct cne_fib *f1 = t->arp_fib < t->rt4_fib ? t->rt4_fib : t->arp_fib;
+    pthread_mutex_lock(&f0->t.dev_lock);
+    if (f1 != f0)
+        pthread_mutex_lock(&f1->t.dev_lock);
+    const struct fwd_fibv arp = {(const uint32_t *)t->arp_fib->t.tbl24, (const uint32_t *)t->arp_fib->t.tbl8, NULL, NULL};
+    const struct fwd_fibv rt = {(const uint32_t *)t->rt4_fib->t.tbl24, (const uint32_t *)t->rt4_fib->t.tbl8, NULL, NULL};
+    const uint32_t *img = t->img;
+    const uint32_t vec = n & ~3u; /* the 4-wide loop's share (:88), then the 1-wide loop (:271) */
+    for (uint32_t i = 0; i < n;) {
+        const uint32_t w = i < vec ? 4u : 1u;
+        struct node_mb x[4];
+        struct fwd_member mem[4];
+        uint32_t hit = 0;
+        for (uint32_t k = 0; k < w; k++) {
+            node_head(mbufs[i + k], readable_end, &x[k]);
+            fwd_rule_direct(img, &arp, x[k].dst, x[k].m != NULL, &mem[k]);
+            hit |= mem[k].a_hit;
+        }
+        for (uint32_t k = 0; k < w; k++)
+            fwd_rule_route(img, &arp, &rt, x[k].m != NULL, hit, &mem[k]);
+        const uint32_t gw0 = mem[0].g_hit ? mem[0].g_idx : CNDP_FWD_NONE;
+        for (uint32_t k = 0; k < w; k++) {
+            if (!x[k].m) {
+                edges[i + k] = (uint16_t)CNDP_FWD_EDGE_NONE;
+                continue;
+            }
+            struct fwd_answer o;
+            fwd_rule_finish(img, &mem[k], k != 0, gw0, &o);
+            edges[i + k] = (uint16_t)o.edge;
+            if (o.ha == CNDP_FWD_NONE || !x[k].adj)
+                continue;
+            /* d_addr at the new mtod + 0, s_addr at + 6, after the TTL / checksum bytes */
+            const uint32_t d[3] = {o.d0, o.d1, o.d2};
+            const uintptr_t eth = x[k].f - x[k].l2;
+            for (uint32_t j = 0; j < 12; j++)
+                if (eth + j < x[k].lim)
+                    *(uint8_t *)(eth + j) = (uint8_t)(d[j >> 2] >> (8u * (j & 3u)));
+        }
+        i += w;
     }
     if (f1 != f0)
         pthread_mutex_unlock(&f1->t.dev_lock);

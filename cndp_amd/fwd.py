@@ -98,6 +98,19 @@ class FwdTable:
         return out
 
 
+def node_host(tbl: FwdTable, ptrs, n: int | None = None, readable_end=None) -> np.ndarray:
+    """cndp_fwd_node_host (include/cndp_mqcnet.h): the ip4_forward node on the
+    calling thread over one burst of n <= 256 mbufs (a ctypes array of
+    pktmbuf_t addresses as MbufPool.ptrs gives it, or its address), the frames
+    and the mbufs' data_off / data_len edited in place.  readable_end: the
+    address at which the mbufs' region ends, None for each mbuf's own
+    buf_addr + buf_len.  Returns the edges, CNDP_MQ_EDGE_FWD_GATEWAY included."""
+    n = len(ptrs) if n is None else n
+    edges = np.zeros(max(n, 1), np.uint16)
+    N.check(N.lib().cndp_fwd_node_host(tbl.h, ptrs, n, edges.ctypes.data, readable_end), "cndp_fwd_node_host")
+    return edges[:n]
+
+
 def alloc_fwd_outputs(n: int, device) -> dict:
     """The output arrays of cndp_gpu_ip4_forward as torch tensors (signed
     dtypes of the same width, as Classifier.alloc_outputs uses)."""

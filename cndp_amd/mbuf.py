@@ -112,15 +112,18 @@ class MbufQueue:
 
     def __init__(self, cl, mode: int, flags: int = 0, batch: int = 8192, depth: int = 4,
                  max_delay_us: int = 50, umem=None, lport: int = 0, stage_max: int = 0, metadata=None,
-                 fib=None, acl=None, acl_mode: int = N.CNDP_ACL_STRICT, acl_flags: int = 0, lports=()):
+                 fib=None, acl=None, acl_mode: int = N.CNDP_ACL_STRICT, acl_flags: int = 0, lports=(),
+                 fwd_tbl=None):
         """metadata: cnet's pktmbuf_metadata hook, a Python function of the mbuf
         address returning the metadata address (None: m + 64).
         cndpfwd modes (CNDP_MQ_CFWD_FWD / _L3FWD / CNDP_MQ_ACL_FWD, cndp_mqfwd.h):
         lport is the incoming port, lports the ports that exist, fib the l3fwd
         FIB (cfwd.l3fwd_fib), acl an AclTable with acl_mode / acl_flags; the
-        FIB and the table must outlive the queue."""
+        FIB and the table must outlive the queue.
+        CNDP_MQ_IP4_FORWARD (cndp_mqcnet.h): fwd_tbl is the FwdTable the node
+        resolves in; it must outlive the queue."""
         self._L = N.lib()
-        self._keep = (fib, acl)
+        self._keep = (fib, acl, fwd_tbl)
         c = N.MqConf()
         c.mode, c.flags, c.batch, c.depth = mode, flags, batch, depth
         c.max_delay_us, c.stage_max, c.lport = max_delay_us, stage_max, lport
@@ -140,6 +143,9 @@ class MbufQueue:
                 w.lport_mask[k] = bits
             N.check(self._L.cndp_gpu_mq_create_fwd(cl.h, ctypes.byref(c), ctypes.byref(w), ctypes.byref(h)),
                     "cndp_gpu_mq_create_fwd")
+        elif fwd_tbl is not None:
+            N.check(self._L.cndp_gpu_mq_create_ip4_forward(cl.h, ctypes.byref(c), fwd_tbl.h, ctypes.byref(h)),
+                    "cndp_gpu_mq_create_ip4_forward")
         else:
             N.check(self._L.cndp_gpu_mq_create(cl.h, ctypes.byref(c), ctypes.byref(h)), "cndp_gpu_mq_create")
         self.h = h

@@ -1,7 +1,8 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
 include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h,
-include/cndp_acl.h, include/cndp_cfwd.h and include/cndp_mqfwd.h).
+include/cndp_acl.h, include/cndp_cfwd.h, include/cndp_mqfwd.h and
+include/cndp_mqcnet.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -147,6 +148,11 @@ CNDP_MQ_EDGE_ACL_DENY = 0xFFFC
 CNDP_MQ_EDGE_ACL_PREFILTER = 0xFFFB
 (CNDP_MQ_STAT_FORWARD, CNDP_MQ_STAT_ECHO, CNDP_MQ_STAT_ACL_PREFILTER, CNDP_MQ_STAT_ACL_DENY,
  CNDP_MQ_STAT_ACL_PERMIT) = range(3, 8)
+# cndp_mqcnet.h
+CNDP_MQ_IP4_FORWARD = 7
+CNDP_MQ_EDGE_FWD_GATEWAY = 0x0400
+CNDP_MQ_EDGE_FWD_MASK = 0x01FF
+CNDP_MQ_STAT_FWD_DIRECT, CNDP_MQ_STAT_FWD_GATEWAY, CNDP_MQ_STAT_FWD_ARP_REQUEST = range(8, 11)
 
 
 def CNDP_L4_EDGE(node: int, e: int) -> int:
@@ -387,6 +393,7 @@ def lib():
         "cndp_gpu_set_tuning": (c_int, [c_void_p, c_int, c_int]),
         "cndp_gpu_mq_create": (c_int, [c_void_p, POINTER(MqConf), POINTER(c_void_p)]),
         "cndp_gpu_mq_create_fwd": (c_int, [c_void_p, POINTER(MqConf), POINTER(MqFwd), POINTER(c_void_p)]),
+        "cndp_gpu_mq_create_ip4_forward": (c_int, [c_void_p, POINTER(MqConf), c_void_p, POINTER(c_void_p)]),
         "cndp_gpu_mq_free": (None, [c_void_p]),
         "cndp_gpu_mq_submit": (c_int, [c_void_p, c_void_p, c_uint32]),
         "cndp_gpu_mq_flush": (c_int, [c_void_p]),
@@ -433,6 +440,8 @@ def lib():
         "cndp_fwd_max_netif": (c_int, [c_void_p]),
         "cndp_fwd_lookup": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
         "cndp_gpu_ip4_forward": (c_int, [c_void_p, c_void_p, POINTER(Batch), c_uint32, POINTER(FwdIo), c_void_p]),
+        # cndp_mqcnet.h
+        "cndp_fwd_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
         # cndp_tx.h
         "cndp_pcb_tx_set": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
         "cndp_pcb_tx_get": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
@@ -473,7 +482,7 @@ def exported_symbols():
     import re
     names = []
     inc = os.path.join(os.path.dirname(HERE), "include")
-    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h"):
+    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h", "cndp_mqcnet.h"):
         with open(os.path.join(inc, h)) as f:
             txt = f.read()
         names += re.findall(r"^[A-Za-z_][\w \*]*?\b((?:cne|cndp|ip4)_\w+)\s*\(", txt, re.M)

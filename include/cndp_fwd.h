@@ -22,7 +22,8 @@
  *  - the node's cached next_index (ip4_forward.c:69,210-268,306-317): it only
  *    decides how the per-edge streams are filled, never a frame's edge;
  *  - the mbuf's data_off / data_len adjustment (pktmbuf_adjust, :115,279): a
- *    batch carries frames, not mbufs.
+ *    batch carries frames, not mbufs (over mbufs: the queue mode and the host
+ *    node of cndp_mqcnet.h, which make it).
  * Where the reference's behaviour is undefined this build defines it:
  *  - a frame of a 4-wide group without a route object has no gateway: no
  *    lookup is made and it counts as a miss (:162-175 read gateway[k]

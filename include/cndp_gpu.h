@@ -223,7 +223,9 @@ typedef struct cndp_gpu_mq cndp_gpu_mq_t;
 #define CNDP_MQ_MAC_SWAP 2u
 #define CNDP_MQ_IP4_REWRITE 3u
 /* modes 4-6, cndpfwd's fwd / l3fwd / ACL loops, need tables: cndp_mqfwd.h
- * (cndp_gpu_mq_create_fwd); cndp_gpu_mq_create answers -EINVAL for them */
+ * (cndp_gpu_mq_create_fwd); mode 7, cnet's ip4_forward node, needs a forwarding
+ * table: cndp_mqcnet.h (cndp_gpu_mq_create_ip4_forward); cndp_gpu_mq_create
+ * answers -EINVAL for them */
 #define CNDP_MQ_F_HASH (1u << 0)
 #define CNDP_MQ_F_NO_METADATA (1u << 1) /* cnet: leave cnet_metadata unwritten */
 /* Zero-copy ip4_lookup and cnet: the host hands over mbuf pointers only and
