@@ -60,7 +60,8 @@ class Classifier:
                    cnet_fold: int | None = None, spec_grid: int | None = None,
                    spec_lists: int | None = None, spec_types: int | None = None,
                    stream_bal: int | None = None, spec_wait: int | None = None,
-                   host_window: int | None = None, fib_lds: int | None = None):
+                   host_window: int | None = None, fib_lds: int | None = None,
+                   mq_pcb_lds: int | None = None):
         """Kernel variant knobs (cndp_gpu_set_tuning); never change results
         (spec_wait, the speculation pass's wait bound in us, -1 = fault
         injection, turns an expired wait into -EIO, never into other edges)."""
@@ -68,6 +69,7 @@ class Classifier:
                        (N.CNDP_TUNE_SPEC_WAIT, spec_wait), (N.CNDP_TUNE_HOST_WINDOW, host_window),
                        (N.CNDP_TUNE_SPEC_LISTS, spec_lists), (N.CNDP_TUNE_SPEC_TYPES, spec_types),
                        (N.CNDP_TUNE_STREAM_BAL, stream_bal), (N.CNDP_TUNE_FIB_LDS, fib_lds),
+                       (N.CNDP_TUNE_MQ_PCB_LDS, mq_pcb_lds),
                        (N.CNDP_TUNE_NT, nt), (N.CNDP_TUNE_UNROLL, unroll),
                        (N.CNDP_TUNE_BLOCKS_PER_CU, blocks_per_cu), (N.CNDP_TUNE_TILE, tile),
                        (N.CNDP_TUNE_DIR16, dir16), (N.CNDP_TUNE_CNET_TILE, cnet_tile),

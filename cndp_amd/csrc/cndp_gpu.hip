@@ -37,6 +37,8 @@
 #include "../../include/cndp_mqfwd.h"
 #include "fwd_internal.h"           // the ip4_forward queue mode's group rule and its table's reader protocol
 #include "../../include/cndp_mqcnet.h"
+#include "pcb_internal.h"           // the udp_input queue mode's per-frame rule and its table's reader protocol
+#include "../../include/cndp_mql4.h"
 
 #define CNDP_VERSION "cndp_amd 0.1 (gfx950)"
 
@@ -4668,6 +4670,8 @@ struct cndp_gpu_ctx {
     int tune_tile;        // CNDP_TUNE_TILE
     int tune_dir16;       // CNDP_TUNE_DIR16
     int tune_fib_lds;     // CNDP_TUNE_FIB_LDS: 0 off, 1 on where the image fits
+    int tune_mq_pcb_lds;  // CNDP_TUNE_MQ_PCB_LDS: the udp_input queue kernel looks up in an LDS copy of the image
+    int mq_pcb_lds_ok;    // that kernel may take its LDS (hipFuncSetAttribute succeeded; 0: not asked yet)
     int fib_lds_ok;       // the image kernels may take their LDS (hipFuncSetAttribute succeeded)
     uint64_t n_fib_lds;   // CNDP_STAT_FIB_LDS: classify launches that took the LDS-image kernel
     int tune_cnet_tile;   // CNDP_TUNE_CNET_TILE
@@ -7788,6 +7792,217 @@ __global__ __launch_bounds__(MQ_TPB) void k_mq_ip4_forward(MqArgs a, MqIpf w)
     mq_complete(a);
 }
 
+// cnet's ip4_proto + udp_input nodes (cndp_mql4.h, ip4_proto.c:30-195,
+// udp_input.c:43-123).  A block is one wave; a lane owns one mbuf for the
+// demux: ip4_proto on header byte 9, the key, the BEST_MATCH lookup in the
+// table image where it lies in device memory (pcb_udp_lookup, pcb_internal.h:
+// the text cndp_udp_input_node_host runs; the image is at most 90 KiB, read by
+// every wave of every batch, so it stays in L2), and whether the PCB asks for a
+// checksum verify.  The verifies stay inside the wave: a ballot lists the lanes
+// that need one, a wave-uniform loop takes up to four of them a turn, and each
+// 16-lane group sums one datagram -- the owner's addresses, length and
+// pseudo-header sum travel by shuffle, the loads are 16-byte aligned ones with
+// head and tail masked, the per-lane byte sums are reduced across the group, and
+// the verdict returns to the owner by shuffle.  All 64 lanes run every turn, so
+// no cross-lane operation is divergent.  No LDS, no second launch, no atomic
+// but mq_complete's ticket.
+//   a.off[i]   zero-copy: the device address of mtod (0: the mbuf or the frame
+//              lies outside every registered region); staged: the offset of the
+//              frame's copy in the staging, a multiple of 16
+//   a.priv[i]  l3_len | readable bytes from mtod << 16 | front << 32 |
+//              back << 36: up to 15 bytes in front of mtod and behind the
+//              readable bytes that an aligned load may touch (zero-copy: they
+//              lie in the frame's region; staged: the copy's zeroed tail)
+// Bytes past the readable ones read as zero; a 16-byte load that would leave
+// [mtod - front, mtod + readable + back) is made byte by byte inside the
+// datagram instead.  Nothing is written but the edge and one 16-byte record per
+// mbuf into pinned memory: {edge | PCB index << 16, ports, faddr, laddr}; poll
+// makes the node's edits from it (mq_writeback).
+#define MQ_UDP_R_SHIFT 16u
+#define MQ_UDP_FRONT_SHIFT 32u
+#define MQ_UDP_BACK_SHIFT 36u
+#define MQ_UDP_NOIDX 0xFFFFu
+#define MQ_UDP_LDS_MAX (128u * 1024u) // the largest image is 22532 words, 88 KiB
+
+// dword at address y of a datagram occupying [lo, hi): bytes outside read as zero
+__device__ __forceinline__ uint32_t mq_udp_mask(uint32_t d, uintptr_t y, uintptr_t lo, uintptr_t hi)
+{
+    uint32_t mk = 0xffffffffu;
+    if (lo > y) {
+        const uintptr_t k = lo - y;
+        mk = k >= 4 ? 0u : mk << (8u * (uint32_t)k);
+    }
+    if (hi < y + 4) {
+        const uintptr_t k = hi > y ? hi - y : 0;
+        mk &= k == 0 ? 0u : 0xffffffffu >> (8u * (4u - (uint32_t)k));
+    }
+    return d & mk;
+}
+
+// LDS (CNDP_TUNE_MQ_PCB_LDS, the measured alternative; off by default): the
+// block -- one wave -- first copies the whole image, header included, into dynamic LDS and looks up there.
+extern __shared__ uint32_t mq_udp_lds[];
+
+template <bool LDS>
+__global__ __launch_bounds__(MQ_TPB) void k_mq_udp_input(MqArgs a, const uint32_t *__restrict__ gimg)
+{
+    const uint32_t lane = threadIdx.x, gl = lane & 15u, grp = lane >> 4;
+    const uint32_t *img = gimg;
+    if (LDS) {
+        const uint32_t words = gimg[3];
+        for (uint32_t k = lane; k < words; k += MQ_TPB)
+            mq_udp_lds[k] = gimg[k];
+        __syncthreads();
+        img = mq_udp_lds;
+    }
+    const uint32_t flags = img[2];
+    for (uint32_t base = blockIdx.x * MQ_TPB; base < a.n; base += gridDim.x * MQ_TPB) {
+        const uint32_t i = base + lane;
+        const bool live = i < a.n;
+        const uint8_t *p = nullptr;
+        uint32_t R = 0, l3 = 0, front = 0, back = 0;
+        if (live) {
+            const uint64_t pv = a.priv[i], o = a.off[i];
+            l3 = (uint32_t)pv & 0x1ffu;
+            R = (uint32_t)(pv >> MQ_UDP_R_SHIFT) & 0xffffu;
+            front = (uint32_t)(pv >> MQ_UDP_FRONT_SHIFT) & 15u;
+            back = (uint32_t)(pv >> MQ_UDP_BACK_SHIFT) & 15u;
+            if (!a.zc)
+                p = o <= a.slab_len && R <= a.slab_len - o ? a.slab + o : nullptr; // never from mq_fill
+            else
+                p = (const uint8_t *)(uintptr_t)o;
+        }
+        const bool taken = p != nullptr;
+        uint32_t edge = MQ_EDGE_NONE, idx = MQ_UDP_NOIDX, ports = 0, faddr = 0, laddr = 0, L = 0;
+        bool need = false;
+        if (taken) {
+            const uint32_t w0 = mqf_le32(p, R, 0);
+            faddr = mqf_le32(p, R, 12);
+            laddr = mqf_le32(p, R, 16);
+            const uint32_t pe = pcb_ip4_proto(mqf_byte(p, R, 9), flags);
+            if (pe) {
+                edge = CNDP_MQ_EDGE(CNDP_MQ_NODE_IP4_PROTO, pe - 1u);
+            } else {
+                ports = mqf_le32(p, R, l3);
+                const uint32_t ckf = mqf_byte(p, R, l3 + 6u) | mqf_byte(p, R, l3 + 7u);
+                const uint32_t idf = pcb_udp_lookup(img, laddr, faddr, ports >> 16, ports & 0xffffu);
+                if (idf == CNDP_PCB_NONE) {
+                    edge = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT,
+                                        (flags & PCB_F_PUNT) ? CNDP_UDP_INPUT_PKT_PUNT : CNDP_UDP_INPUT_PKT_DROP);
+                } else {
+                    idx = idf & PCB_IDXF_IDX;
+                    edge = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_CHNL_RECV);
+                    if ((idf & PCB_IDXF_CKSUM) && ckf) {
+                        // __ipv4_udptcp_cksum: total_length < header length sums to 0, which fails
+                        const uint32_t ihl = (w0 & 0xfu) * 4u, tot = ((w0 >> 8) & 0xff00u) | (w0 >> 24);
+                        if (tot < ihl) {
+                            edge = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_PKT_DROP) | CNDP_MQ_EDGE_L4_CKSUM;
+                        } else {
+                            need = true;
+                            L = tot - ihl;
+                        }
+                    }
+                }
+            }
+        }
+        // what a verify's group needs of its owner: the datagram's readable part [lo, lo + dlen),
+        // how far in front of lo and behind its end a load may reach, the pseudo-header sum
+        const uint32_t d0 = l3 < R ? l3 : R, d1 = l3 + L < R ? l3 + L : R; // d0 <= d1 <= R
+        const uintptr_t lo_own = (uintptr_t)p + d0;
+        const uint32_t dlen_own = need ? d1 - d0 : 0u;
+        const uint32_t flo_own = d0 + front, fhi_own = R - d1 + back;
+        const uint32_t ph_own = pcb_udp_phdr_sum(faddr, laddr, 17u, L);
+        bool bad = false;
+        unsigned long long todo = __ballot(need);
+        while (todo) { // wave-uniform: every lane runs every turn
+            int own = -1; // this 16-lane group's datagram: the grp-th lowest lane still to do
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) {
+                if (todo) {
+                    if (k == grp)
+                        own = __ffsll((long long)todo) - 1;
+                    todo &= todo - 1ull;
+                }
+            }
+            const int src = own >= 0 ? own : 0;
+            const uintptr_t lo = (uintptr_t)__shfl((uint32_t)lo_own, src, 64) |
+                                 (uintptr_t)__shfl((uint32_t)((uint64_t)lo_own >> 32), src, 64) << 32;
+            const uint32_t dl = __shfl(dlen_own, src, 64);
+            const uint32_t dlen = own >= 0 ? dl : 0u; // a group without a datagram this turn sums nothing
+            const uint32_t flo = __shfl(flo_own, src, 64), fhi = __shfl(fhi_own, src, 64);
+            const uint32_t ph = __shfl(ph_own, src, 64);
+            uint32_t se = 0, so = 0; // sums of the bytes at even / odd addresses
+            if (dlen) {
+                const uintptr_t hi = lo + dlen, alo = lo - flo, ahi = hi + fhi;
+                const uintptr_t A = lo & ~(uintptr_t)15;
+                const uint32_t nch = (uint32_t)((hi - A + 15u) / 16u);
+                for (uint32_t c = gl; c < nch; c += 16u) {
+                    const uintptr_t X = A + 16u * (uintptr_t)c;
+                    if (X >= alo && X + 16 <= ahi) {
+                        const u32x4 v = *(const u32x4 *)X;
+                        uint32_t d[4] = {v.x, v.y, v.z, v.w};
+                        if (X < lo || X + 16 > hi) {
+#pragma unroll
+                            for (int q = 0; q < 4; q++)
+                                d[q] = mq_udp_mask(d[q], X + 4u * q, lo, hi);
+                        }
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            se = __builtin_amdgcn_sad_u8(d[q] & 0x00ff00ffu, 0u, se);
+                            so = __builtin_amdgcn_sad_u8((d[q] >> 8) & 0x00ff00ffu, 0u, so);
+                        }
+                    } else { // a chunk that overhangs what may be touched: the datagram's own bytes
+                        const uintptr_t x0 = X > lo ? X : lo, x1 = X + 16 < hi ? X + 16 : hi;
+                        for (uintptr_t x = x0; x < x1; x++) {
+                            const uint32_t bv = *(const uint8_t *)x;
+                            if (x & 1u)
+                                so += bv;
+                            else
+                                se += bv;
+                        }
+                    }
+                }
+            }
+            // words are little-endian pairs counted from the datagram's first byte
+            uint32_t S = (lo & 1u) ? so + (se << 8) : se + (so << 8);
+#pragma unroll
+            for (int sh = 8; sh >= 1; sh >>= 1)
+                S += __shfl_xor(S, sh, 64);
+            const uint32_t ok = pcb_udp_cksum_ok(S, ph);
+#pragma unroll
+            for (int k = 0; k < 4; k++) { // the verdict back to its owner
+                const int ok_own = __shfl(own, k * 16, 64);
+                const uint32_t ok_v = __shfl(ok, k * 16, 64);
+                if (ok_own == (int)lane)
+                    bad = !ok_v;
+            }
+        }
+        if (bad) { // verify < 0: pkt_drop, userptr left unset
+            edge = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_PKT_DROP) | CNDP_MQ_EDGE_L4_CKSUM;
+            idx = MQ_UDP_NOIDX;
+        }
+        if (live) {
+            u32x4 r;
+            r.x = edge | idx << 16;
+            r.y = ports;
+            r.z = faddr;
+            r.w = laddr;
+            a.rec[i] = r;
+            a.edges[i] = (uint16_t)edge;
+        }
+    }
+    mq_complete(a);
+}
+
+// the LDS variant may take more than the 64 KiB a kernel gets by default: 1 = granted
+static int mq_udp_lds_init(void)
+{
+    const int ok = hipFuncSetAttribute((const void *)k_mq_udp_input<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)MQ_UDP_LDS_MAX) == hipSuccess;
+    (void)hipGetLastError();
+    return ok;
+}
+
 // ip4_rewrite_node_process (ip4_rewrite.c:40-247) per packet of the node's
 // bursts: the next hop's rewrite data at mtod (:85), TTL = priv1.ttl - 1 and
 // the checksum from priv1.cksum + htons(0x0100) -- in the 4-wide loop with
@@ -8121,6 +8336,8 @@ struct cndp_gpu_mq {
     uint64_t n_fwd[CNDP_MQ_STAT_ACL_PERMIT + 1]; // their counters by CNDP_MQ_STAT_* key, counted by poll
     cndp_fwd_tbl_t *ipf;           // CNDP_MQ_IP4_FORWARD (cndp_gpu_mq_create_ip4_forward): the forwarding table
     uint64_t n_ipf[3];             // its counters, CNDP_MQ_STAT_FWD_DIRECT + k, counted by poll
+    cndp_pcb_tbl_t *pcb;           // CNDP_MQ_UDP_INPUT (cndp_gpu_mq_create_udp_input): the PCB table
+    uint64_t n_l4[6];              // its counters, CNDP_MQ_STAT_L4_RECV + k, counted by poll
     MqSlot slot[CNDP_MQ_DEPTH_MAX];
 };
 
@@ -8164,15 +8381,17 @@ static inline bool mq_is_fwd(uint32_t mode)
 }
 
 // fwd: the tables of a cndpfwd mode, checked by cndp_gpu_mq_create_fwd; ipf: the forwarding table of
-// CNDP_MQ_IP4_FORWARD, checked by cndp_gpu_mq_create_ip4_forward; both nullptr for the node modes
+// CNDP_MQ_IP4_FORWARD, checked by cndp_gpu_mq_create_ip4_forward; pcb: the PCB table of CNDP_MQ_UDP_INPUT,
+// checked by cndp_gpu_mq_create_udp_input; all nullptr for the node modes
 static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const struct cndp_mq_fwd *fwd,
-                     cndp_fwd_tbl_t *ipf, cndp_gpu_mq_t **out)
+                     cndp_fwd_tbl_t *ipf, cndp_pcb_tbl_t *pcb, cndp_gpu_mq_t **out)
 {
     if (!c || !conf || !out)
         return -EINVAL;
     *out = nullptr;
     struct cndp_mq_conf k = *conf;
-    if (ipf ? k.mode != CNDP_MQ_IP4_FORWARD
+    if (pcb ? k.mode != CNDP_MQ_UDP_INPUT
+        : ipf ? k.mode != CNDP_MQ_IP4_FORWARD
         : fwd ? !mq_is_fwd(k.mode)
               : (k.mode != CNDP_MQ_IP4_LOOKUP && k.mode != CNDP_MQ_CNET && k.mode != CNDP_MQ_MAC_SWAP &&
                  k.mode != CNDP_MQ_IP4_REWRITE))
@@ -8211,6 +8430,7 @@ static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const s
     if (fwd)
         q->fwd = *fwd;
     q->ipf = ipf;
+    q->pcb = pcb;
     if (k.umem) {
         // zero-copy: every region the context holds (the UMEMs of all the
         // graph's ports), conf.umem among them
@@ -8231,9 +8451,11 @@ static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const s
     const uint64_t B = k.batch;
     const bool cnet = k.mode == CNDP_MQ_CNET, rw = k.mode == CNDP_MQ_IP4_REWRITE;
     const bool acl = k.mode == CNDP_MQ_ACL_FWD, cfwd = mq_is_fwd(k.mode), fw4 = k.mode == CNDP_MQ_IP4_FORWARD;
+    const bool udp = k.mode == CNDP_MQ_UDP_INPUT;
     const bool zc = q->zc != 0;
     q->stage = zc ? 0u
              : cnet ? (uint32_t)al64(k.stage_max)
+             : udp ? ((k.stage_max + 15u) & ~15u) // at most: a frame takes its readable bytes rounded up to 16
              : k.mode == CNDP_MQ_IP4_LOOKUP ? ((k.flags & CNDP_MQ_F_RX_PARSE) ? 32u : MQ_W4)
              : k.mode == CNDP_MQ_MAC_SWAP || k.mode == CNDP_MQ_CFWD_FWD ? MQ_SWAP
              : cfwd ? MQ_FWD_STAGE
@@ -8241,12 +8463,13 @@ static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const s
     q->h_mb = 0;                                          // zc: mbuf device addresses; rewrite: tail flags
     q->h_off = al64(B * 8);                               // frame words / offsets
     q->h_len = q->h_off + al64(B * 8);                    // cnet: length fields; rewrite: priv1; acl: data_len;
-                                                          // ip4_forward: l2_len | MQ_IPF_ADJ | back << 8
-    q->h_md = q->h_len + (cnet || rw || acl || fw4 ? al64(B * 8) : 0); // cnet zc: metadata addresses
+                                                          // ip4_forward: l2_len | MQ_IPF_ADJ | back << 8;
+                                                          // udp_input: l3_len | readable << 16 | front << 32 | back << 36
+    q->h_md = q->h_len + (cnet || rw || acl || fw4 || udp ? al64(B * 8) : 0); // cnet zc: metadata addresses
     q->h_edge = q->h_md + (cnet && zc ? al64(B * 8) : 0);
     q->hostwb = zc && (k.flags & CNDP_MQ_F_HOST_WRITEBACK);
     q->h_rec = q->h_edge + al64(B * 2);                   // staged (and host writeback): records
-    q->h_rmd = q->h_rec + ((zc && !q->hostwb) || rw || cfwd || fw4 || k.mode == CNDP_MQ_MAC_SWAP ? 0 : al64(B * (cnet ? 16 : 8)));
+    q->h_rmd = q->h_rec + ((zc && !q->hostwb && !udp) || rw || cfwd || fw4 || k.mode == CNDP_MQ_MAC_SWAP ? 0 : al64(B * (cnet || udp ? 16 : 8)));
     q->h_stage = q->h_rmd + (q->hostwb && cnet ? B * 32 : 0); // cnet host writeback: metadata addresses
     q->h_bst = q->h_stage + B * q->stage;                 // CNDP_MQ_F_REWRITE: burst starts; ip4_forward: chunk words
     q->h_bytes = q->h_bst + ((k.flags & CNDP_MQ_F_REWRITE) || fw4 ? al64((B + 1) * 4) : 0);
@@ -8292,7 +8515,7 @@ fail:
 
 extern "C" int cndp_gpu_mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, cndp_gpu_mq_t **out)
 {
-    return mq_create(c, conf, nullptr, nullptr, out);
+    return mq_create(c, conf, nullptr, nullptr, nullptr, out);
 }
 
 // cndp_mqfwd.h: the argument rules of the three cndpfwd modes, then the queue as for every mode
@@ -8327,7 +8550,7 @@ extern "C" int cndp_gpu_mq_create_fwd(cndp_gpu_ctx_t *c, const struct cndp_mq_co
         if (!built)
             return -ENOENT;
     }
-    return mq_create(c, conf, fwd, nullptr, out);
+    return mq_create(c, conf, fwd, nullptr, nullptr, out);
 }
 
 // cndp_mqcnet.h: cnet's ip4_forward node over a forwarding table
@@ -8342,7 +8565,22 @@ extern "C" int cndp_gpu_mq_create_ip4_forward(cndp_gpu_ctx_t *c, const struct cn
     const int r = fwd_dev_check(tbl, c->dev); // one table, one device, as cndp_gpu_ip4_forward has it
     if (r)
         return r;
-    return mq_create(c, conf, nullptr, tbl, out);
+    return mq_create(c, conf, nullptr, tbl, nullptr, out);
+}
+
+// cndp_mql4.h: cnet's ip4_proto + udp_input nodes over a PCB table
+extern "C" int cndp_gpu_mq_create_udp_input(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf,
+                                            cndp_pcb_tbl_t *tbl, cndp_gpu_mq_t **out)
+{
+    if (!c || !conf || !tbl || !out)
+        return -EINVAL;
+    *out = nullptr;
+    if (conf->mode != CNDP_MQ_UDP_INPUT || conf->flags)
+        return -EINVAL;
+    const int r = pcb_dev_check(tbl, c->dev); // one table, one device, as cndp_gpu_udp_input has it
+    if (r)
+        return r;
+    return mq_create(c, conf, nullptr, nullptr, tbl, out);
 }
 
 extern "C" void cndp_gpu_mq_free(cndp_gpu_mq_t *q)
@@ -8507,6 +8745,22 @@ static int mq_launch_kernels(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t slot_i)
         hipLaunchKernelGGL(k_mq_ip4_forward, dim3(sl->nb < 65536u ? sl->nb : 65536u), dim3(MQ_TPB), 0, s, a, w);
         const bool ok = hipGetLastError() == hipSuccess;
         r = fwd_dev_end(q->ipf, s, ok);
+        if (!ok || r)
+            return ok ? r : -EIO;
+    } else if (q->conf.mode == CNDP_MQ_UDP_INPUT) {
+        // the table's reader protocol (pcb_internal.h): ordered after a reader on another stream,
+        // the image mirrored on this one, our end recorded for the next reader
+        const uint32_t *img = nullptr;
+        if ((r = pcb_dev_begin(q->pcb, c->dev, s, &img)))
+            return r;
+        // the table's lock is held between begin and end: img_words is the mirrored image's
+        const uint32_t lds = q->pcb->img_words * 4u;
+        if (c->tune_mq_pcb_lds && c->mq_pcb_lds_ok && lds <= MQ_UDP_LDS_MAX)
+            hipLaunchKernelGGL(k_mq_udp_input<true>, dim3(g), dim3(MQ_TPB), lds, s, a, img);
+        else
+            hipLaunchKernelGGL(k_mq_udp_input<false>, dim3(g), dim3(MQ_TPB), 0, s, a, img);
+        const bool ok = hipGetLastError() == hipSuccess;
+        r = pcb_dev_end(q->pcb, s, ok);
         if (!ok || r)
             return ok ? r : -EIO;
     } else if (q->conf.mode == CNDP_MQ_IP4_REWRITE) {
@@ -8745,6 +8999,37 @@ static void mq_fill(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k
         const uint32_t j = sl->n + i;
         uint8_t *f = buf + doff; // pktmbuf_mtod
         sl->mb[j] = m;
+        if (mode == CNDP_MQ_UDP_INPUT) {
+            // the readable bytes: data_len clipped at the buffer's end, then at the frame's
+            // region's end (zero-copy) or at stage_max (staged, copied into a 16-byte-aligned,
+            // zero-padded place of the staging); front / back: what an aligned load may overhang
+            const uint32_t l3 = (uint32_t)((*(const uint64_t *)(m + MB_TX_OFFLOAD) >> 7) & 0x1FFu);
+            uint64_t R = dlen < room ? dlen : room, front = 0, back;
+            if (zc) {
+                const int kf = mq_region(q, m, 64) < 0 ? -1 : mq_region(q, f, 1);
+                if (kf < 0) {
+                    hoff[j] = hlen[j] = 0; // not taken
+                    continue;
+                }
+                const MqRegion &g = q->rg[kf];
+                const uint64_t in_front = (uint64_t)(f - g.host), left = g.len - in_front;
+                R = R < left ? R : left;
+                front = in_front < 15u ? in_front : 15u;
+                back = left - R < 15u ? left - R : 15u;
+                hoff[j] = (uint64_t)(intptr_t)(f + g.delta);
+            } else {
+                R = R < q->conf.stage_max ? R : q->conf.stage_max;
+                const uint64_t span = R > 16u ? (R + 15u) & ~15ull : 16u;
+                uint8_t *dst = H + q->h_stage + sl->stage_used;
+                memcpy(dst, f, R);
+                memset(dst + R, 0, span - R);
+                back = span - R < 15u ? span - R : 15u;
+                hoff[j] = sl->stage_used;
+                sl->stage_used += span;
+            }
+            hlen[j] = l3 | R << MQ_UDP_R_SHIFT | front << MQ_UDP_FRONT_SHIFT | back << MQ_UDP_BACK_SHIFT;
+            continue;
+        }
         if (cnet) {
             u32x2 l;
             l.x = (uint32_t)dlen | (room << 16);
@@ -8909,6 +9194,42 @@ static void mq_writeback(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
 {
     const uint32_t mode = q->conf.mode;
     const uint16_t *ed = (const uint16_t *)(sl->h + q->h_edge);
+    if (mode == CNDP_MQ_UDP_INPUT) {
+        // every edit of the two nodes from the device's records, zero-copy or staged
+        // (pcb_udp_apply, pcb_internal.h: the text the host twin runs), and the six counters
+        const u32x4 *rec = (const u32x4 *)(sl->h + q->h_rec);
+        uint16_t *edw = (uint16_t *)(sl->h + q->h_edge);
+        for (uint32_t i = i0; i < i1; i++) {
+            if (i + MQ_PF < i1)
+                __builtin_prefetch(sl->mb[i + MQ_PF], 1);
+            const uint32_t e = edw[i];
+            if (e == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
+                continue;
+            if ((e >> 8) == CNDP_MQ_NODE_IP4_PROTO) {
+                q->n_l4[(e & 0xFFu) == CNDP_IP4_PROTO_TCP ? CNDP_MQ_STAT_L4_TCP - CNDP_MQ_STAT_L4_RECV
+                                                          : CNDP_MQ_STAT_L4_PROTO_DROP - CNDP_MQ_STAT_L4_RECV]++;
+                continue;
+            }
+            uint8_t *m = (uint8_t *)sl->mb[i];
+            uint8_t *md = mq_md_host(q, m);
+            if (!md) { // udp_input.c:57-59
+                edw[i] = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_PKT_DROP);
+                q->n_l4[CNDP_MQ_STAT_L4_NOMD - CNDP_MQ_STAT_L4_RECV]++;
+                continue;
+            }
+            const u32x4 r = rec[i];
+            const uint32_t idx = r.x >> 16;
+            const bool recv = e == CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_CHNL_RECV);
+            uint64_t user = 0;
+            if (recv && idx < q->pcb->max) // a value set while the batch was in flight may or may not show
+                user = __atomic_load_n(&q->pcb->user[idx], __ATOMIC_RELAXED);
+            pcb_udp_apply(m, md, e, user, r.y, r.z, r.w);
+            q->n_l4[recv                          ? 0
+                    : (e & CNDP_MQ_EDGE_L4_CKSUM) ? CNDP_MQ_STAT_L4_CKSUM - CNDP_MQ_STAT_L4_RECV
+                                                  : CNDP_MQ_STAT_L4_NOMATCH - CNDP_MQ_STAT_L4_RECV]++;
+        }
+        return;
+    }
     if (mode == CNDP_MQ_IP4_FORWARD) {
         // pktmbuf_adjust(m, -l2_len) on the host, zero-copy or staged; staged also the frame
         // bytes, in the reference's order: TTL / checksum at the old mtod, then the MAC bytes at
@@ -9213,6 +9534,17 @@ extern "C" int64_t cndp_gpu_mq_stat(const cndp_gpu_mq_t *q, int key)
         return (int64_t)q->n_ipf[CNDP_FWD_STAT_GATEWAY];
     case CNDP_MQ_STAT_FWD_ARP_REQUEST:
         return (int64_t)q->n_ipf[CNDP_FWD_STAT_ARP_REQUEST];
+    case CNDP_MQ_STAT_L4_RECV: // cndp_mql4.h
+    case CNDP_MQ_STAT_L4_NOMATCH:
+    case CNDP_MQ_STAT_L4_CKSUM:
+    case CNDP_MQ_STAT_L4_PROTO_DROP:
+    case CNDP_MQ_STAT_L4_TCP:
+    case CNDP_MQ_STAT_L4_NOMD:
+        // known to a CNDP_MQ_UDP_INPUT queue only: on every other mode these keys stay the
+        // unknown keys they were before the mode existed
+        if (q->conf.mode != CNDP_MQ_UDP_INPUT)
+            return -EINVAL;
+        return (int64_t)q->n_l4[key - CNDP_MQ_STAT_L4_RECV];
     default:
         return -EINVAL;
     }
@@ -9341,6 +9673,17 @@ extern "C" int cndp_gpu_set_tuning(cndp_gpu_ctx_t *c, int key, int value)
         if (value < 0 || value > 1)
             return -EINVAL;
         c->tune_fib_lds = value;
+        return 0;
+    case CNDP_TUNE_MQ_PCB_LDS:
+        if (value < 0 || value > 1)
+            return -EINVAL;
+        if (value && !c->mq_pcb_lds_ok) {
+            const int r = set_device(c->dev);
+            if (r)
+                return r;
+            c->mq_pcb_lds_ok = mq_udp_lds_init();
+        }
+        c->tune_mq_pcb_lds = value;
         return 0;
     case CNDP_TUNE_SPEC_WAIT:
         if (value == 0 || value < -1 || value > 40000000)

@@ -14,6 +14,11 @@
 //                    masked, per-lane integer byte sums, a cross-lane reduction,
 //                    then the reference's own folds.
 // Every frame read is bounded by slab_len; no load leaves the slab.
+//
+// The image's device mirror is one buffer guarded by an event.  Every reader --
+// cndp_gpu_udp_input here, the mbuf queue's CNDP_MQ_UDP_INPUT kernel in
+// cndp_gpu.hip -- brackets its launch with pcb_dev_begin / pcb_dev_end
+// (pcb_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <errno.h>
@@ -475,11 +480,16 @@ static int l4_dev_get(struct cndp_pcb_tbl *t, int dev, L4Dev **out)
     return 0;
 }
 
-static int l4_run(L4Dev *d, struct cndp_pcb_tbl *t, const struct cndp_batch *b,
-                  const struct cndp_l4_io *io, hipStream_t s)
+// pcb_dev_begin under t->lock: the device, the host image, the wait for a
+// reader on another stream, the mirror brought up to date
+static int l4_begin_locked(struct cndp_pcb_tbl *t, int dev, hipStream_t s, L4Dev **out)
 {
-    int r = pcb_image(t);
+    HIP_TRY(hipSetDevice(dev));
+    L4Dev *d = NULL;
+    int r = l4_dev_get(t, dev, &d);
     if (r)
+        return r;
+    if ((r = pcb_image(t)))
         return r;
     if (d->have_last && d->last != s)
         HIP_TRY(hipStreamWaitEvent(s, d->ev, 0));
@@ -496,8 +506,54 @@ static int l4_run(L4Dev *d, struct cndp_pcb_tbl *t, const struct cndp_batch *b,
         HIP_TRY(hipStreamSynchronize(s)); // the host table may change after we return
         d->gen = t->img_gen;
     }
-    if (b->n == 0)
+    *out = d;
+    return 0;
+}
+
+// pcb_dev_end under t->lock: the reader's end recorded
+static int l4_end_locked(struct cndp_pcb_tbl *t, hipStream_t s, int launched)
+{
+    L4Dev *d = (L4Dev *)t->dev;
+    if (!launched || !d)
         return 0;
+    HIP_TRY(hipEventRecord(d->ev, s));
+    d->last = s;
+    d->have_last = 1;
+    return 0;
+}
+
+extern "C" int pcb_dev_begin(struct cndp_pcb_tbl *t, int dev, void *stream, const uint32_t **img)
+{
+    pthread_mutex_lock(&t->lock);
+    L4Dev *d = NULL;
+    const int r = l4_begin_locked(t, dev, (hipStream_t)stream, &d);
+    if (r) {
+        pthread_mutex_unlock(&t->lock);
+        return r;
+    }
+    *img = d->img;
+    return 0;
+}
+
+extern "C" int pcb_dev_end(struct cndp_pcb_tbl *t, void *stream, int launched)
+{
+    const int r = l4_end_locked(t, (hipStream_t)stream, launched);
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+extern "C" int pcb_dev_check(struct cndp_pcb_tbl *t, int dev)
+{
+    pthread_mutex_lock(&t->lock);
+    const L4Dev *d = (const L4Dev *)t->dev;
+    const int r = d && d->dev != dev ? -EINVAL : 0; // one table, one device
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+static int l4_run(L4Dev *d, struct cndp_pcb_tbl *t, const struct cndp_batch *b,
+                  const struct cndp_l4_io *io, hipStream_t s)
+{
     // demux grid: sized from the CU count and the LDS the table image takes
     const uint32_t lds = (t->img_words - PCB_IMG_HDR) * 4u;
     uint32_t per_cu = lds ? L4_LDS_MAX / lds : L4_BLOCKS_PER_CU;
@@ -544,9 +600,6 @@ static int l4_run(L4Dev *d, struct cndp_pcb_tbl *t, const struct cndp_batch *b,
     // costs a launch that exits at once, never a second pass over the frames
     hipLaunchKernelGGL(l4_cksum_kernel, dim3(grid), dim3(L4_BLOCK), 0, s, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev, s));
-    d->last = s;
-    d->have_last = 1;
     return 0;
 }
 
@@ -565,9 +618,13 @@ extern "C" int cndp_gpu_udp_input(cndp_gpu_ctx_t *ctx, cndp_pcb_tbl_t *tbl, cons
         r = -EINVAL;
     L4Dev *d = NULL;
     if (!r)
-        r = l4_dev_get(tbl, dev, &d);
-    if (!r)
-        r = l4_run(d, tbl, b, io, (hipStream_t)stream);
+        r = l4_begin_locked(tbl, dev, (hipStream_t)stream, &d);
+    if (!r) {
+        if (b->n)
+            r = l4_run(d, tbl, b, io, (hipStream_t)stream);
+        const int e = l4_end_locked(tbl, (hipStream_t)stream, b->n && !r);
+        r = r ? r : e;
+    }
     pthread_mutex_unlock(&tbl->lock);
     return r;
 }

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "pcb_internal.h"
+#include "../../include/cndp_mql4.h"
 
 static uint32_t pow2_ceil(uint32_t v)
 {
@@ -33,13 +34,17 @@ int cndp_pcb_create(uint32_t max_entries, cndp_pcb_tbl_t **out)
     t->vec = calloc(max_entries, sizeof(*t->vec));
     t->closed = calloc(max_entries, 1);
     t->img = calloc(words, sizeof(uint32_t));
-    if (!t->vec || !t->closed || !t->img || pthread_mutex_init(&t->lock, NULL)) {
+    t->user = calloc(max_entries, sizeof(uint64_t));
+    if (!t->vec || !t->closed || !t->img || !t->user || pthread_mutex_init(&t->lock, NULL)) {
         free(t->vec);
         free(t->closed);
         free(t->img);
+        free(t->user);
         free(t);
         return -ENOMEM;
     }
+    for (uint32_t i = 0; i < max_entries; i++)
+        t->user[i] = i;
     t->max = max_entries;
     t->flags = PCB_F_PUNT;
     t->gen = 1;
@@ -64,6 +69,7 @@ void cndp_pcb_free(cndp_pcb_tbl_t *t)
     free(t->closed);
     free(t->img);
     free(t->timg);
+    free(t->user);
     free(t);
 }
 
@@ -99,6 +105,7 @@ int cndp_pcb_del(cndp_pcb_tbl_t *t, uint32_t idx)
     else { /* cnet_pcb_free: memset 0, and the vector keeps the entry */
         memset(&t->vec[idx], 0, sizeof(t->vec[idx]));
         t->closed[idx] = 1;
+        __atomic_store_n(&t->user[idx], (uint64_t)idx, __ATOMIC_RELAXED);
         t->gen++;
     }
     pthread_mutex_unlock(&t->lock);
@@ -309,4 +316,120 @@ int cndp_pcb_lookup_indexed(cndp_pcb_tbl_t *t, const struct cndp_pcb_key *keys, 
         idx_out[k] = pcb_tcp_lookup(t->timg, keys[k].laddr, keys[k].faddr, keys[k].lport, keys[k].fport);
     pthread_mutex_unlock(&t->lock);
     return r;
+}
+
+/* ---- cndp_mql4.h: the user values and the two nodes over mbufs on the host --- */
+int cndp_pcb_user_set(cndp_pcb_tbl_t *t, uint32_t idx, uint64_t user)
+{
+    if (!t)
+        return -EINVAL;
+    int r = 0;
+    pthread_mutex_lock(&t->lock);
+    if (idx >= t->count)
+        r = -EINVAL;
+    else /* cndp_gpu_mq_poll reads it without the lock */
+        __atomic_store_n(&t->user[idx], user, __ATOMIC_RELAXED);
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+int cndp_pcb_user_get(cndp_pcb_tbl_t *t, uint32_t idx, uint64_t *user)
+{
+    if (!t || !user)
+        return -EINVAL;
+    int r = 0;
+    pthread_mutex_lock(&t->lock);
+    if (idx >= t->count)
+        r = -EINVAL;
+    else
+        *user = t->user[idx];
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+/* byte o of a frame with R readable bytes: bytes past them read as zero */
+static inline uint32_t fr8(const uint8_t *f, uint32_t R, uint32_t o) { return o < R ? f[o] : 0u; }
+
+static inline uint32_t fr32(const uint8_t *f, uint32_t R, uint32_t o)
+{
+    return fr8(f, R, o) | fr8(f, R, o + 1u) << 8 | fr8(f, R, o + 2u) << 16 | fr8(f, R, o + 3u) << 24;
+}
+
+int cndp_udp_input_node_host(cndp_pcb_tbl_t *t, void *const *mbufs, uint32_t n, uint16_t *edges,
+                             const void *readable_end, uint32_t stage_max, void *(*metadata)(const void *m))
+{
+    if (!t || n > 256u || (n && (!mbufs || !edges)))
+        return -EINVAL;
+    pthread_mutex_lock(&t->lock);
+    int r = pcb_image(t);
+    if (r) {
+        pthread_mutex_unlock(&t->lock);
+        return r;
+    }
+    const uint32_t *img = t->img;
+    const uint32_t flags = img[2];
+    const uintptr_t end = (uintptr_t)readable_end;
+    for (uint32_t i = 0; i < n; i++) {
+        uint8_t *m = (uint8_t *)mbufs[i];
+        edges[i] = (uint16_t)CNDP_MQ_EDGE_NONE;
+        if (!m || (end && (uintptr_t)m + 64u > end))
+            continue;
+        uint64_t buf, txo;
+        uint16_t doff, blen, dlen;
+        memcpy(&buf, m + PCB_MB_BUF_ADDR, 8);
+        memcpy(&txo, m + PCB_MB_TX_OFFLOAD, 8);
+        memcpy(&doff, m + PCB_MB_DATA_OFF, 2);
+        memcpy(&blen, m + PCB_MB_BUF_LEN, 2);
+        memcpy(&dlen, m + PCB_MB_DATA_LEN, 2);
+        const uintptr_t fa = (uintptr_t)buf + doff;
+        if (end && fa >= end)
+            continue; /* the frame lies outside the region */
+        const uint8_t *f = (const uint8_t *)fa;
+        /* the readable bytes: data_len, clipped at the buffer's end, the region's and stage_max */
+        uint32_t R = dlen;
+        const uint32_t room = blen > doff ? (uint32_t)(blen - doff) : 0u;
+        R = R < room ? R : room;
+        if (end && end - fa < R)
+            R = (uint32_t)(end - fa);
+        if (stage_max && stage_max < R)
+            R = stage_max;
+        const uint32_t l3 = (uint32_t)((txo >> 7) & 0x1ffu);
+        const uint32_t pe = pcb_ip4_proto(fr8(f, R, 9), flags);
+        if (pe) {
+            edges[i] = CNDP_MQ_EDGE(CNDP_MQ_NODE_IP4_PROTO, pe - 1u);
+            continue;
+        }
+        uint8_t *md = metadata ? (uint8_t *)metadata(m) : m + 64;
+        if (!md) {
+            edges[i] = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_PKT_DROP);
+            continue;
+        }
+        const uint32_t faddr = fr32(f, R, 12), laddr = fr32(f, R, 16), ports = fr32(f, R, l3);
+        const uint32_t ckf = fr8(f, R, l3 + 6u) | fr8(f, R, l3 + 7u);
+        const uint32_t idf = pcb_udp_lookup(img, laddr, faddr, ports >> 16, ports & 0xffffu);
+        uint32_t e;
+        if (idf == CNDP_PCB_NONE) {
+            e = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT,
+                             (flags & PCB_F_PUNT) ? CNDP_UDP_INPUT_PKT_PUNT : CNDP_UDP_INPUT_PKT_DROP);
+        } else {
+            e = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_CHNL_RECV);
+            if ((idf & PCB_IDXF_CKSUM) && ckf) {
+                const uint32_t ihl = (fr8(f, R, 0) & 0xfu) * 4u, tot = fr8(f, R, 2) << 8 | fr8(f, R, 3);
+                uint32_t ok = 0;
+                if (tot >= ihl) { /* __ipv4_udptcp_cksum: below it the sum is 0, which fails */
+                    const uint32_t L = tot - ihl;
+                    uint32_t S = 0;
+                    for (uint32_t k = 0; k < L && l3 + k < R; k++)
+                        S += (k & 1u) ? (uint32_t)f[l3 + k] << 8 : (uint32_t)f[l3 + k];
+                    ok = pcb_udp_cksum_ok(S, pcb_udp_phdr_sum(faddr, laddr, 17u, L));
+                }
+                if (!ok)
+                    e = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_PKT_DROP) | CNDP_MQ_EDGE_L4_CKSUM;
+            }
+        }
+        edges[i] = (uint16_t)e;
+        pcb_udp_apply(m, md, e, idf == CNDP_PCB_NONE ? 0u : t->user[idf & PCB_IDXF_IDX], ports, faddr, laddr);
+    }
+    pthread_mutex_unlock(&t->lock);
+    return 0;
 }

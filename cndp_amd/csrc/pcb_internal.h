@@ -6,8 +6,10 @@
 #include <pthread.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/cndp_tcp.h" /* includes cndp_l4.h */
+#include "../../include/cndp_mql4.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -65,10 +67,164 @@ struct cndp_pcb_tbl {
     uint64_t ximg_gen;      /* gen the transmit image was built from (0 = never) */
     void *xdev;             /* the transmit stage's device mirror, owned by cndp_tx.hip */
     void (*xdev_release)(void *xdev);
+    /* host only (cndp_pcb_user_set, cndp_mql4.h): per entry what udp_input stores in
+     * m->userptr, the entry's index by default; max values, never part of an image */
+    uint64_t *user;
 };
 
 /* Call with tbl->lock held: bring tbl->img up to date.  0 or -ENOMEM. */
 int pcb_image(struct cndp_pcb_tbl *tbl);
+
+/* Readers of the image's device mirror (cndp_l4.hip): cndp_gpu_udp_input and the
+ * mbuf queue's CNDP_MQ_UDP_INPUT kernel in cndp_gpu.hip.  pcb_dev_begin takes
+ * tbl->lock, binds the table to device `dev` (-EINVAL when it is bound to
+ * another), orders `stream` after the last reader when that was on another
+ * stream, brings the host image and the mirror up to date (a copy is waited
+ * for, so the table may change once the lock is dropped) and hands out the
+ * mirror's address.  On 0 the lock is held until pcb_dev_end, which records the
+ * reader's end on `stream` when `launched` and drops it; on an error it is not. */
+int pcb_dev_begin(struct cndp_pcb_tbl *tbl, int dev, void *stream, const uint32_t **img);
+int pcb_dev_end(struct cndp_pcb_tbl *tbl, void *stream, int launched);
+/* -EINVAL when the table's mirror lives on another device than `dev`, else 0 */
+int pcb_dev_check(struct cndp_pcb_tbl *tbl, int dev);
+
+/* ---- ip4_proto + udp_input per frame (cndp_mql4.h): the text the queue's
+ * kernel k_mq_udp_input and the host twin cndp_udp_input_node_host both compile */
+
+/* ip4_proto (ip4_proto.c:30-195) on header byte 9 with the table's flags:
+ * 0 = on to udp_input, else 1 + the node's edge (drop 0, tcp_input 2) */
+static inline PCB_HD uint32_t pcb_ip4_proto(uint32_t proto, uint32_t flags)
+{
+    if (proto == 17u)
+        return 0u;
+    return proto == 6u && (flags & PCB_F_TCP) ? 1u + CNDP_IP4_PROTO_TCP : 1u + CNDP_IP4_PROTO_DROP;
+}
+
+/* pcb_v4_lookup, BEST_MATCH, answered from the UDP image `img`: the port
+ * directory, then a walk of that port's run, which is in vector order, so the
+ * first entry with the fewest wildcards wins and an exact match ends the walk.
+ * Returns the entry's idxf value (its vector index | PCB_IDXF_CKSUM) or
+ * CNDP_PCB_NONE. */
+static inline PCB_HD uint32_t pcb_udp_lookup(const uint32_t *img, uint32_t laddr, uint32_t faddr, uint32_t lport,
+                                             uint32_t fport)
+{
+    const uint32_t n = img[0], H = img[1];
+    const uint32_t *t_laddr = img + PCB_IMG_HDR, *t_faddr = t_laddr + n, *t_ports = t_faddr + n;
+    const uint32_t *slots = t_ports + n;
+    const uint16_t *idxf = (const uint16_t *)(slots + H);
+    uint32_t s;
+    for (uint32_t h = pcb_port_hash(lport, H);; h = (h + 1u) & (H - 1u)) {
+        s = slots[h];
+        if (!(s & PCB_SLOT_VALID))
+            return CNDP_PCB_NONE;
+        if (((s >> 12) & 0xffffu) == lport)
+            break;
+    }
+    uint32_t bestw = 3, bestj = 0;
+    for (uint32_t j = s & 0xfffu; j < n; j++) {
+        const uint32_t pp = t_ports[j];
+        if ((pp >> 16) != lport)
+            break;
+        const uint32_t el = t_laddr[j], ef = t_faddr[j];
+        uint32_t w = 0;
+        if (el != 0) {
+            if (laddr == 0)
+                w++;
+            else if (el != laddr)
+                continue;
+        } else if (laddr != 0)
+            w++;
+        if (ef != 0) {
+            if (faddr == 0)
+                w++;
+            else if (ef != faddr || (pp & 0xffffu) != fport)
+                continue;
+        } else if (faddr != 0)
+            w++;
+        if (w < bestw) {
+            bestw = w;
+            bestj = j;
+            if (w == 0)
+                break;
+        }
+    }
+    return bestw == 3 ? CNDP_PCB_NONE : (uint32_t)idxf[bestj];
+}
+
+/* The folds of cne_ipv4_udptcp_cksum_verify (net/cne_ip.h:131-178, :235-260,
+ * :275-349) once the datagram's bytes are summed: S = the sum of its bytes at
+ * even offsets + 256 * the sum of those at odd offsets (its little-endian 16-bit
+ * words, a last odd byte as a low byte), below 2^32 for every length; faddr /
+ * laddr / proto as loaded from the header, L = total_length - IHL * 4.
+ * 1 = the verify passes. */
+static inline PCB_HD uint32_t pcb_udp_phdr_sum(uint32_t faddr, uint32_t laddr, uint32_t proto, uint32_t L)
+{
+    uint32_t ph = (faddr & 0xffffu) + (faddr >> 16) + (laddr & 0xffffu) + (laddr >> 16) + ((proto & 0xffu) << 8) +
+                  (((L & 0xffu) << 8) | ((L >> 8) & 0xffu));
+    ph = (ph >> 16) + (ph & 0xffffu);
+    ph = (ph >> 16) + (ph & 0xffffu);
+    return ph & 0xffffu;
+}
+
+static inline PCB_HD uint32_t pcb_udp_cksum_ok(uint32_t S, uint32_t ph)
+{
+    S = (S >> 16) + (S & 0xffffu); /* cne_raw_cksum's reduce */
+    S = (S >> 16) + (S & 0xffffu);
+    S &= 0xffffu;
+    uint32_t c = S + ph;           /* + cne_ipv4_phdr_cksum, __ipv4_udptcp_cksum's fold */
+    c = ((c >> 16) + (c & 0xffffu)) & 0xffffu;
+    return c == 0xffffu;
+}
+
+/* pktmbuf_t fields (pktmbuf.h:102-204) and struct cnet_metadata {faddr, laddr}
+ * (cnet_meta.h:20-25), two struct in_caddr of 20 bytes (cne_inet.h:37-45) */
+#define PCB_MB_BUF_ADDR 8
+#define PCB_MB_DATA_OFF 24
+#define PCB_MB_BUF_LEN 28
+#define PCB_MB_DATA_LEN 30
+#define PCB_MB_TX_OFFLOAD 40
+#define PCB_MB_USERPTR 56
+#define PCB_MD_LADDR 20
+#define PCB_AF_INET 2
+
+/* udp_input's writes for one mbuf whose edge is a udp_input edge and whose
+ * metadata is md (udp_input.c:95-96, :110-120), on the host: the twin makes
+ * them as it goes, cndp_gpu_mq_poll from the device's record.  user is the
+ * matched PCB's user value (chnl_recv only). */
+static inline void pcb_udp_apply(uint8_t *m, uint8_t *md, uint32_t edge, uint64_t user, uint32_t ports, uint32_t faddr,
+                                 uint32_t laddr)
+{
+    const uint16_t fport = (uint16_t)ports, lport = (uint16_t)(ports >> 16);
+    memcpy(md + 2, &fport, 2);
+    memcpy(md + PCB_MD_LADDR + 2, &lport, 2);
+    if (edge & CNDP_MQ_EDGE_L4_CKSUM)
+        return; /* verify < 0: userptr and the header stay */
+    if ((edge & 0xffu) != CNDP_UDP_INPUT_CHNL_RECV) {
+        memset(m + PCB_MB_USERPTR, 0, 8); /* m->userptr = NULL */
+        return;
+    }
+    memcpy(m + PCB_MB_USERPTR, &user, 8);
+    md[0] = md[PCB_MD_LADDR] = PCB_AF_INET; /* in_caddr_copy of the key: the rest of the union is zero */
+    md[1] = md[PCB_MD_LADDR + 1] = 4;
+    memcpy(md + 4, &faddr, 4);
+    memset(md + 8, 0, 12);
+    memcpy(md + PCB_MD_LADDR + 4, &laddr, 4);
+    memset(md + PCB_MD_LADDR + 8, 0, 12);
+    /* pktmbuf_adj_offset(m, l3_len + l4_len), pktmbuf.h:961-971 */
+    uint64_t txo;
+    uint16_t doff, blen, dlen;
+    memcpy(&txo, m + PCB_MB_TX_OFFLOAD, 8);
+    memcpy(&doff, m + PCB_MB_DATA_OFF, 2);
+    memcpy(&blen, m + PCB_MB_BUF_LEN, 2);
+    memcpy(&dlen, m + PCB_MB_DATA_LEN, 2);
+    const uint32_t len = (uint32_t)((txo >> 7) & 0x1ffu) + (uint32_t)((txo >> 16) & 0xffu);
+    if (len > dlen || len + doff > blen)
+        return;
+    doff = (uint16_t)(doff + len);
+    dlen = (uint16_t)(dlen - len);
+    memcpy(m + PCB_MB_DATA_OFF, &doff, 2);
+    memcpy(m + PCB_MB_DATA_LEN, &dlen, 2);
+}
 
 /* TCP index image (u32 words), rebuilt by pcb_tcp_image() when the table changed.
  * A TCP vector is thousands of connections on a few listening ports, so a key is

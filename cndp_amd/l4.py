@@ -133,6 +133,38 @@ class PcbTable:
                 "cndp_pcb_lookup_indexed")
         return out
 
+    def user_set(self, idx: int, user: int) -> int:
+        """cndp_pcb_user_set (include/cndp_mql4.h): the value the udp_input node
+        stores in m->userptr for this PCB; returns its result (0 or -errno)."""
+        return self._L.cndp_pcb_user_set(self.h, idx, user & 0xFFFFFFFFFFFFFFFF)
+
+    def user_get(self, idx: int) -> int:
+        """cndp_pcb_user_get: the PCB's user value (its index unless one was set)."""
+        v = ctypes.c_uint64()
+        N.check(self._L.cndp_pcb_user_get(self.h, idx, ctypes.byref(v)), "cndp_pcb_user_get")
+        return int(v.value)
+
+
+METADATA_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p)
+
+
+def udp_input_node_host(tbl: PcbTable, ptrs, n: int | None = None, readable_end=None, stage_max: int = 0,
+                        metadata=None) -> np.ndarray:
+    """cndp_udp_input_node_host (include/cndp_mql4.h): ip4_proto + udp_input on
+    the calling thread over one burst of n <= 256 mbufs (a ctypes array of
+    pktmbuf_t addresses as MbufPool.ptrs gives it, or its address), the mbufs'
+    userptr / data_off / data_len and their metadata edited in place.
+    readable_end: the address at which the mbufs' region ends (None: no region);
+    stage_max: the staged queue's clip (0: none); metadata: pktmbuf_metadata as
+    a Python function of the mbuf address (None: m + 64).  Returns the edges."""
+    n = len(ptrs) if n is None else n
+    edges = np.zeros(max(n, 1), np.uint16)
+    fn = METADATA_FN(metadata) if metadata else None
+    N.check(N.lib().cndp_udp_input_node_host(tbl.h, ptrs, n, edges.ctypes.data, readable_end, stage_max,
+                                             ctypes.cast(fn, ctypes.c_void_p) if fn else None),
+            "cndp_udp_input_node_host")
+    return edges[:n]
+
 
 def alloc_l4_outputs(n: int, device) -> dict:
     """The output arrays of cndp_gpu_udp_input as torch tensors (signed

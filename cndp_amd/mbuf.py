@@ -113,7 +113,7 @@ class MbufQueue:
     def __init__(self, cl, mode: int, flags: int = 0, batch: int = 8192, depth: int = 4,
                  max_delay_us: int = 50, umem=None, lport: int = 0, stage_max: int = 0, metadata=None,
                  fib=None, acl=None, acl_mode: int = N.CNDP_ACL_STRICT, acl_flags: int = 0, lports=(),
-                 fwd_tbl=None):
+                 fwd_tbl=None, pcb_tbl=None):
         """metadata: cnet's pktmbuf_metadata hook, a Python function of the mbuf
         address returning the metadata address (None: m + 64).
         cndpfwd modes (CNDP_MQ_CFWD_FWD / _L3FWD / CNDP_MQ_ACL_FWD, cndp_mqfwd.h):
@@ -121,9 +121,12 @@ class MbufQueue:
         FIB (cfwd.l3fwd_fib), acl an AclTable with acl_mode / acl_flags; the
         FIB and the table must outlive the queue.
         CNDP_MQ_IP4_FORWARD (cndp_mqcnet.h): fwd_tbl is the FwdTable the node
-        resolves in; it must outlive the queue."""
+        resolves in; it must outlive the queue.
+        CNDP_MQ_UDP_INPUT (cndp_mql4.h): pcb_tbl is the PcbTable ip4_proto +
+        udp_input demultiplex in; it must outlive the queue.  metadata is the
+        hook poll calls (returning 0 / None stands for NULL)."""
         self._L = N.lib()
-        self._keep = (fib, acl, fwd_tbl)
+        self._keep = (fib, acl, fwd_tbl, pcb_tbl)
         c = N.MqConf()
         c.mode, c.flags, c.batch, c.depth = mode, flags, batch, depth
         c.max_delay_us, c.stage_max, c.lport = max_delay_us, stage_max, lport
@@ -146,6 +149,9 @@ class MbufQueue:
         elif fwd_tbl is not None:
             N.check(self._L.cndp_gpu_mq_create_ip4_forward(cl.h, ctypes.byref(c), fwd_tbl.h, ctypes.byref(h)),
                     "cndp_gpu_mq_create_ip4_forward")
+        elif pcb_tbl is not None:
+            N.check(self._L.cndp_gpu_mq_create_udp_input(cl.h, ctypes.byref(c), pcb_tbl.h, ctypes.byref(h)),
+                    "cndp_gpu_mq_create_udp_input")
         else:
             N.check(self._L.cndp_gpu_mq_create(cl.h, ctypes.byref(c), ctypes.byref(h)), "cndp_gpu_mq_create")
         self.h = h

@@ -1,8 +1,8 @@
 """ctypes binding of libcndp_gpu.so (the C-ABI declared in include/cndp_fib.h,
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
 include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h,
-include/cndp_acl.h, include/cndp_cfwd.h, include/cndp_mqfwd.h and
-include/cndp_mqcnet.h).
+include/cndp_acl.h, include/cndp_cfwd.h, include/cndp_mqfwd.h,
+include/cndp_mqcnet.h and include/cndp_mql4.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -54,6 +54,7 @@ CNDP_TUNE_SPEC_LISTS = 15
 CNDP_TUNE_SPEC_TYPES = 16
 CNDP_TUNE_STREAM_BAL = 17
 CNDP_TUNE_FIB_LDS = 20
+CNDP_TUNE_MQ_PCB_LDS = 21
 CNDP_TUNE_SPEC_WAIT = 18
 CNDP_TUNE_HOST_WINDOW = 19
 CNDP_MQ_IP4_LOOKUP, CNDP_MQ_CNET, CNDP_MQ_MAC_SWAP, CNDP_MQ_IP4_REWRITE = 0, 1, 2, 3
@@ -153,6 +154,18 @@ CNDP_MQ_IP4_FORWARD = 7
 CNDP_MQ_EDGE_FWD_GATEWAY = 0x0400
 CNDP_MQ_EDGE_FWD_MASK = 0x01FF
 CNDP_MQ_STAT_FWD_DIRECT, CNDP_MQ_STAT_FWD_GATEWAY, CNDP_MQ_STAT_FWD_ARP_REQUEST = range(8, 11)
+# cndp_mql4.h
+CNDP_MQ_UDP_INPUT = 8
+CNDP_MQ_NODE_IP4_PROTO = 3
+CNDP_MQ_NODE_UDP_INPUT = 4
+CNDP_MQ_EDGE_L4_CKSUM = 0x0080
+CNDP_MQ_EDGE_L4_MASK = 0xFF7F
+(CNDP_MQ_STAT_L4_RECV, CNDP_MQ_STAT_L4_NOMATCH, CNDP_MQ_STAT_L4_CKSUM, CNDP_MQ_STAT_L4_PROTO_DROP,
+ CNDP_MQ_STAT_L4_TCP, CNDP_MQ_STAT_L4_NOMD) = range(11, 17)
+
+
+def CNDP_MQ_EDGE(node: int, e: int) -> int:
+    return (node << 8) | e
 
 
 def CNDP_L4_EDGE(node: int, e: int) -> int:
@@ -394,6 +407,7 @@ def lib():
         "cndp_gpu_mq_create": (c_int, [c_void_p, POINTER(MqConf), POINTER(c_void_p)]),
         "cndp_gpu_mq_create_fwd": (c_int, [c_void_p, POINTER(MqConf), POINTER(MqFwd), POINTER(c_void_p)]),
         "cndp_gpu_mq_create_ip4_forward": (c_int, [c_void_p, POINTER(MqConf), c_void_p, POINTER(c_void_p)]),
+        "cndp_gpu_mq_create_udp_input": (c_int, [c_void_p, POINTER(MqConf), c_void_p, POINTER(c_void_p)]),
         "cndp_gpu_mq_free": (None, [c_void_p]),
         "cndp_gpu_mq_submit": (c_int, [c_void_p, c_void_p, c_uint32]),
         "cndp_gpu_mq_flush": (c_int, [c_void_p]),
@@ -442,6 +456,10 @@ def lib():
         "cndp_gpu_ip4_forward": (c_int, [c_void_p, c_void_p, POINTER(Batch), c_uint32, POINTER(FwdIo), c_void_p]),
         # cndp_mqcnet.h
         "cndp_fwd_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
+        # cndp_mql4.h
+        "cndp_udp_input_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p]),
+        "cndp_pcb_user_set": (c_int, [c_void_p, c_uint32, ctypes.c_uint64]),
+        "cndp_pcb_user_get": (c_int, [c_void_p, c_uint32, POINTER(ctypes.c_uint64)]),
         # cndp_tx.h
         "cndp_pcb_tx_set": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
         "cndp_pcb_tx_get": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
@@ -482,7 +500,7 @@ def exported_symbols():
     import re
     names = []
     inc = os.path.join(os.path.dirname(HERE), "include")
-    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h", "cndp_mqcnet.h"):
+    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h", "cndp_mqcnet.h", "cndp_mql4.h"):
         with open(os.path.join(inc, h)) as f:
             txt = f.read()
         names += re.findall(r"^[A-Za-z_][\w \*]*?\b((?:cne|cndp|ip4)_\w+)\s*\(", txt, re.M)

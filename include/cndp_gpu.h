@@ -224,8 +224,9 @@ typedef struct cndp_gpu_mq cndp_gpu_mq_t;
 #define CNDP_MQ_IP4_REWRITE 3u
 /* modes 4-6, cndpfwd's fwd / l3fwd / ACL loops, need tables: cndp_mqfwd.h
  * (cndp_gpu_mq_create_fwd); mode 7, cnet's ip4_forward node, needs a forwarding
- * table: cndp_mqcnet.h (cndp_gpu_mq_create_ip4_forward); cndp_gpu_mq_create
- * answers -EINVAL for them */
+ * table: cndp_mqcnet.h (cndp_gpu_mq_create_ip4_forward); mode 8, cnet's
+ * ip4_proto + udp_input nodes, needs a PCB table: cndp_mql4.h
+ * (cndp_gpu_mq_create_udp_input); cndp_gpu_mq_create answers -EINVAL for them */
 #define CNDP_MQ_F_HASH (1u << 0)
 #define CNDP_MQ_F_NO_METADATA (1u << 1) /* cnet: leave cnet_metadata unwritten */
 /* Zero-copy ip4_lookup and cnet: the host hands over mbuf pointers only and
@@ -472,7 +473,12 @@ int cndp_gpu_bin_ids(cndp_gpu_ctx_t *ctx, uint32_t mode, const uint32_t *nh, con
  *                           memory; a larger image, or a device that refuses the kernel
  *                           its LDS, takes the gathering kernel.  0 = always the gathering
  *                           kernel.  A new context takes its value from the environment
- *                           variable of the same name when set */
+ *                           variable of the same name when set
+ *   CNDP_TUNE_MQ_PCB_LDS    the mbuf queue's CNDP_MQ_UDP_INPUT kernel (cndp_mql4.h): 0 = the
+ *                           lookup reads the PCB table image in device memory (default),
+ *                           1 = every block copies the image into LDS first and looks up
+ *                           there (the measured alternative); a device
+ *                           that refuses the kernel its LDS takes the default */
 #define CNDP_TUNE_NT 1
 #define CNDP_TUNE_UNROLL 2
 #define CNDP_TUNE_BLOCKS_PER_CU 3
@@ -493,6 +499,7 @@ int cndp_gpu_bin_ids(cndp_gpu_ctx_t *ctx, uint32_t mode, const uint32_t *nh, con
 #define CNDP_TUNE_SPEC_WAIT 18
 #define CNDP_TUNE_HOST_WINDOW 19
 #define CNDP_TUNE_FIB_LDS 20
+#define CNDP_TUNE_MQ_PCB_LDS 21
 int cndp_gpu_set_tuning(cndp_gpu_ctx_t *ctx, int key, int value);
 
 /* Observability: the last cnet classify's shape, read from pinned host words
