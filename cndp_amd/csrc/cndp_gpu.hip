@@ -8309,9 +8309,63 @@ struct MqRegion {
     int64_t delta; // device address - host address
 };
 
+typedef void (*mq_fill_fn)(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k);
+typedef void (*mq_wb_fn)(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1);
+
+// One entry per CNDP_MQ_* mode (mq_modes[], below the hooks): what the mode accepts, what a
+// slot's blocks hold for it, and the places where the modes differ.  The queue's functions
+// (create, submit, launch, poll, stat) read the entry and call its hooks; none of them tests
+// conf.mode.
+#define MQ_BY_PLAIN 0u // cndp_gpu_mq_create
+#define MQ_BY_FWD 1u   // cndp_gpu_mq_create_fwd
+#define MQ_BY_IPF 2u   // cndp_gpu_mq_create_ip4_forward
+#define MQ_BY_UDP 3u   // cndp_gpu_mq_create_udp_input
+#define MQ_FIB4 1u
+#define MQ_FIB6 2u
+struct MqMode {
+    uint32_t mode;     // its CNDP_MQ_* value (= its index in mq_modes[])
+    uint32_t by;       // MQ_BY_*: the create call it belongs to
+    uint32_t flags;    // the CNDP_MQ_F_* it accepts
+    uint32_t fibs;     // MQ_FIB*: the context FIBs it needs
+    bool wb_hdr;       // host writeback reads the header fields it adjusts: not with CNDP_MQ_F_DEVICE_HEADERS
+    // a slot's pinned block
+    uint32_t stage;    // staged bytes reserved per frame ...
+    uint32_t (*stage_of)(const struct cndp_mq_conf *k); // ... or, where the conf decides, this
+    uint32_t wb_span;  // staged: the frame's first bytes the kernel may change (mq_wb_span copies them back)
+    bool len;          // the h_len array exists
+    uint32_t rec;      // record bytes per mbuf (0, 8, 16), staged and with host writeback ...
+    bool rec_zc;       // ... and zero-copy as well
+    bool md;           // cnet_metadata: its addresses at h_md (zero-copy), the records' at h_rmd (host writeback)
+    bool bst;          // the h_bst array exists ...
+    uint32_t bst_flag; // ... or exists with this flag
+    // a slot's device block
+    bool dev_out;      // it carries the cnet classify outputs
+    bool spec;         // the launch runs the context's ptype speculation: reset when a launch fails,
+                       // its error taken when a batch completes
+    int stat_lo, stat_hi; // the CNDP_MQ_STAT_* keys the mode counts (0, 0: none)
+    // the per-burst header walk into the open slot (room checked by the caller); fill_devhdr: with
+    // CNDP_MQ_F_DEVICE_HEADERS, pointers only (nullptr: the mode ignores the flag)
+    mq_fill_fn fill, fill_devhdr;
+    // optional: the slot cannot take a burst of k although the batch has room
+    bool (*no_room)(const MqSlot *sl, uint32_t k);
+    // optional: per-burst bookkeeping, before the burst's fill (sl->n is still the burst's first mbuf)
+    void (*burst)(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k);
+    // the slot's kernels, after mq_launch_kernels' common arguments; the caller checks hipGetLastError
+    int (*launch)(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a);
+    // results of mbufs [i0, i1) of a finished slot into the mbufs where the kernels did not write
+    // them: zero-copy, staged, zero-copy with host writeback (nullptr: nothing to do)
+    mq_wb_fn wb_zc, wb_staged, wb_host;
+    // optional: counters from the edges poll hands back
+    void (*count)(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k);
+};
+static const MqMode *mq_mode(uint32_t mode, uint32_t by); // nullptr: not a mode of that create call
+
 struct cndp_gpu_mq {
     cndp_gpu_ctx_t *c;
     struct cndp_mq_conf conf;
+    const MqMode *mode;            // conf.mode's entry
+    mq_fill_fn fill;               // its fill or fill_devhdr
+    mq_wb_fn writeback;            // its writeback for this queue's form (nullptr: none)
     hipStream_t s;
     int zc;                        // zero-copy (conf.umem was a registered region)
     MqRegion rg[CNDP_MAX_REGIONS]; // zero-copy: the context's regions when the queue was made
@@ -8331,13 +8385,12 @@ struct cndp_gpu_mq {
     uint32_t head, open, in_flight, seq; // head: oldest slot not fully polled
     uint32_t pending;
     int err;                       // a launch error not yet reported (returned by the next submit)
-    uint64_t n_batches, n_mbufs;   // launched so far (cndp_gpu_mq_stat)
+    // cndp_gpu_mq_stat's counters by CNDP_MQ_STAT_* key: batches and mbufs launched so far, and the
+    // mode's own, counted by poll
+    uint64_t n_stat[CNDP_MQ_STAT_L4_NOMD + 1];
     struct cndp_mq_fwd fwd;        // cndpfwd modes (cndp_gpu_mq_create_fwd): the tables and the known ports
-    uint64_t n_fwd[CNDP_MQ_STAT_ACL_PERMIT + 1]; // their counters by CNDP_MQ_STAT_* key, counted by poll
     cndp_fwd_tbl_t *ipf;           // CNDP_MQ_IP4_FORWARD (cndp_gpu_mq_create_ip4_forward): the forwarding table
-    uint64_t n_ipf[3];             // its counters, CNDP_MQ_STAT_FWD_DIRECT + k, counted by poll
     cndp_pcb_tbl_t *pcb;           // CNDP_MQ_UDP_INPUT (cndp_gpu_mq_create_udp_input): the PCB table
-    uint64_t n_l4[6];              // its counters, CNDP_MQ_STAT_L4_RECV + k, counted by poll
     MqSlot slot[CNDP_MQ_DEPTH_MAX];
 };
 
@@ -8375,38 +8428,57 @@ static inline uint64_t mq_frame_word(cndp_gpu_mq_t *q, const uint8_t *f)
     return ((uint64_t)(intptr_t)(f + q->rg[k].delta) & MQ_ADDR_MASK) | ((left < 255u ? left : 255u) << 56);
 }
 
-static inline bool mq_is_fwd(uint32_t mode)
+// the queue's form (zero-copy, host writeback, device headers), the hooks that go with it, and
+// the byte offsets inside each slot's pinned block (h_*) and device block (d_*)
+static void mq_layout(cndp_gpu_mq_t *q)
 {
-    return mode == CNDP_MQ_CFWD_FWD || mode == CNDP_MQ_CFWD_L3FWD || mode == CNDP_MQ_ACL_FWD;
+    const struct cndp_mq_conf &k = q->conf;
+    const MqMode *m = q->mode;
+    const uint64_t B = k.batch;
+    const bool zc = q->zc != 0;
+    q->hostwb = zc && (k.flags & CNDP_MQ_F_HOST_WRITEBACK);
+    q->devhdr = zc && (k.flags & CNDP_MQ_F_DEVICE_HEADERS) && m->fill_devhdr;
+    q->fill = q->devhdr ? m->fill_devhdr : m->fill;
+    q->writeback = q->hostwb ? m->wb_host : zc ? m->wb_zc : m->wb_staged;
+    q->stage = zc ? 0u : m->stage_of ? m->stage_of(&k) : m->stage;
+    const bool rec = m->rec && (!zc || q->hostwb || m->rec_zc);
+    q->h_mb = 0;                                          // zc: mbuf device addresses; rewrite: tail flags
+    q->h_off = al64(B * 8);                               // frame words / offsets
+    q->h_len = q->h_off + al64(B * 8);                    // what the mode's fill keeps per mbuf beside them
+    q->h_md = q->h_len + (m->len ? al64(B * 8) : 0);      // zc: metadata addresses
+    q->h_edge = q->h_md + (m->md && zc ? al64(B * 8) : 0);
+    q->h_rec = q->h_edge + al64(B * 2);                   // records
+    q->h_rmd = q->h_rec + (rec ? al64(B * m->rec) : 0);   // host writeback: the records' metadata addresses
+    q->h_stage = q->h_rmd + (m->md && q->hostwb ? B * 32 : 0);
+    q->h_bst = q->h_stage + B * q->stage;                 // what the mode's burst hook keeps per burst
+    q->h_bytes = q->h_bst + (m->bst || (k.flags & m->bst_flag) ? al64((B + 1) * 4) : 0);
+    q->d_nh = 0;
+    q->d_edge = q->d_nh + al64(B * 4);
+    q->d_pt = q->d_edge + al64(B);
+    q->d_rm = q->d_pt + al64(B * 4);
+    q->d_hash = q->d_rm + al64(B * 4);
+    q->d_ipl = q->d_hash + al64(B * 4);
+    q->d_win = q->d_ipl + al64(B * 4);
+    q->d_off = q->d_win + (zc ? B * 64 : 0);
+    q->d_len = q->d_off + (m->dev_out && q->devhdr ? al64(B * 8) : 0);
+    q->d_md = q->d_len + (m->dev_out && q->devhdr ? al64(B * 8) : 0);
+    q->d_bytes = m->dev_out ? q->d_md + (q->devhdr ? al64(B * 8) : 0) : 64;
 }
 
-// fwd: the tables of a cndpfwd mode, checked by cndp_gpu_mq_create_fwd; ipf: the forwarding table of
-// CNDP_MQ_IP4_FORWARD, checked by cndp_gpu_mq_create_ip4_forward; pcb: the PCB table of CNDP_MQ_UDP_INPUT,
-// checked by cndp_gpu_mq_create_udp_input; all nullptr for the node modes
-static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const struct cndp_mq_fwd *fwd,
+// by: the create call; fwd: the tables of a cndpfwd mode, checked by cndp_gpu_mq_create_fwd; ipf: the
+// forwarding table of CNDP_MQ_IP4_FORWARD, checked by cndp_gpu_mq_create_ip4_forward; pcb: the PCB
+// table of CNDP_MQ_UDP_INPUT, checked by cndp_gpu_mq_create_udp_input; all nullptr for the node modes
+static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, uint32_t by, const struct cndp_mq_fwd *fwd,
                      cndp_fwd_tbl_t *ipf, cndp_pcb_tbl_t *pcb, cndp_gpu_mq_t **out)
 {
     if (!c || !conf || !out)
         return -EINVAL;
     *out = nullptr;
     struct cndp_mq_conf k = *conf;
-    if (pcb ? k.mode != CNDP_MQ_UDP_INPUT
-        : ipf ? k.mode != CNDP_MQ_IP4_FORWARD
-        : fwd ? !mq_is_fwd(k.mode)
-              : (k.mode != CNDP_MQ_IP4_LOOKUP && k.mode != CNDP_MQ_CNET && k.mode != CNDP_MQ_MAC_SWAP &&
-                 k.mode != CNDP_MQ_IP4_REWRITE))
+    const MqMode *m = mq_mode(k.mode, by);
+    if (!m || (k.flags & ~m->flags))
         return -EINVAL;
-    if (k.flags & ~(CNDP_MQ_F_HASH | CNDP_MQ_F_NO_METADATA | CNDP_MQ_F_DEVICE_HEADERS | CNDP_MQ_F_RX_PARSE |
-                    CNDP_MQ_F_REWRITE | CNDP_MQ_F_HOST_WRITEBACK))
-        return -EINVAL;
-    // host writeback: cnet and ip4_lookup; cnet's poll reads the header fields
-    // it adjusts, so its headers stay on the host, while ip4_lookup's poll only
-    // stores (packet_type, udata64), so its headers may be the device's
-    if ((k.flags & CNDP_MQ_F_HOST_WRITEBACK) &&
-        ((k.mode != CNDP_MQ_CNET && k.mode != CNDP_MQ_IP4_LOOKUP) ||
-         (k.mode == CNDP_MQ_CNET && (k.flags & CNDP_MQ_F_DEVICE_HEADERS))))
-        return -EINVAL;
-    if ((k.flags & (CNDP_MQ_F_RX_PARSE | CNDP_MQ_F_REWRITE)) && k.mode != CNDP_MQ_IP4_LOOKUP)
+    if (m->wb_hdr && (k.flags & CNDP_MQ_F_HOST_WRITEBACK) && (k.flags & CNDP_MQ_F_DEVICE_HEADERS))
         return -EINVAL;
     if ((k.flags & CNDP_MQ_F_REWRITE) && !k.umem) // the rewrite goes into the frame where it lies
         return -EINVAL;
@@ -8417,7 +8489,7 @@ static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const s
     if (k.batch < MQ_BURST || k.batch > (1u << 24) || k.depth < 2 || k.depth > CNDP_MQ_DEPTH_MAX ||
         k.stage_max < 64 || k.stage_max > 65535)
         return -EINVAL;
-    if (k.mode == CNDP_MQ_IP4_LOOKUP ? !c->fib4 : k.mode == CNDP_MQ_CNET ? (!c->fib4 || !c->fib6) : false)
+    if (((m->fibs & MQ_FIB4) && !c->fib4) || ((m->fibs & MQ_FIB6) && !c->fib6))
         return -EINVAL;
     int r = set_device(c->dev);
     if (r)
@@ -8427,6 +8499,7 @@ static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const s
         return -ENOMEM;
     q->c = c;
     q->conf = k;
+    q->mode = m;
     if (fwd)
         q->fwd = *fwd;
     q->ipf = ipf;
@@ -8448,43 +8521,8 @@ static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, const s
         }
         q->zc = 1;
     }
+    mq_layout(q);
     const uint64_t B = k.batch;
-    const bool cnet = k.mode == CNDP_MQ_CNET, rw = k.mode == CNDP_MQ_IP4_REWRITE;
-    const bool acl = k.mode == CNDP_MQ_ACL_FWD, cfwd = mq_is_fwd(k.mode), fw4 = k.mode == CNDP_MQ_IP4_FORWARD;
-    const bool udp = k.mode == CNDP_MQ_UDP_INPUT;
-    const bool zc = q->zc != 0;
-    q->stage = zc ? 0u
-             : cnet ? (uint32_t)al64(k.stage_max)
-             : udp ? ((k.stage_max + 15u) & ~15u) // at most: a frame takes its readable bytes rounded up to 16
-             : k.mode == CNDP_MQ_IP4_LOOKUP ? ((k.flags & CNDP_MQ_F_RX_PARSE) ? 32u : MQ_W4)
-             : k.mode == CNDP_MQ_MAC_SWAP || k.mode == CNDP_MQ_CFWD_FWD ? MQ_SWAP
-             : cfwd ? MQ_FWD_STAGE
-             : fw4 ? MQ_IPF_STAGE : MQ_RW_STAGE;
-    q->h_mb = 0;                                          // zc: mbuf device addresses; rewrite: tail flags
-    q->h_off = al64(B * 8);                               // frame words / offsets
-    q->h_len = q->h_off + al64(B * 8);                    // cnet: length fields; rewrite: priv1; acl: data_len;
-                                                          // ip4_forward: l2_len | MQ_IPF_ADJ | back << 8;
-                                                          // udp_input: l3_len | readable << 16 | front << 32 | back << 36
-    q->h_md = q->h_len + (cnet || rw || acl || fw4 || udp ? al64(B * 8) : 0); // cnet zc: metadata addresses
-    q->h_edge = q->h_md + (cnet && zc ? al64(B * 8) : 0);
-    q->hostwb = zc && (k.flags & CNDP_MQ_F_HOST_WRITEBACK);
-    q->h_rec = q->h_edge + al64(B * 2);                   // staged (and host writeback): records
-    q->h_rmd = q->h_rec + ((zc && !q->hostwb && !udp) || rw || cfwd || fw4 || k.mode == CNDP_MQ_MAC_SWAP ? 0 : al64(B * (cnet || udp ? 16 : 8)));
-    q->h_stage = q->h_rmd + (q->hostwb && cnet ? B * 32 : 0); // cnet host writeback: metadata addresses
-    q->h_bst = q->h_stage + B * q->stage;                 // CNDP_MQ_F_REWRITE: burst starts; ip4_forward: chunk words
-    q->h_bytes = q->h_bst + ((k.flags & CNDP_MQ_F_REWRITE) || fw4 ? al64((B + 1) * 4) : 0);
-    q->d_nh = 0;
-    q->d_edge = q->d_nh + al64(B * 4);
-    q->d_pt = q->d_edge + al64(B);
-    q->d_rm = q->d_pt + al64(B * 4);
-    q->d_hash = q->d_rm + al64(B * 4);
-    q->d_ipl = q->d_hash + al64(B * 4);
-    q->d_win = q->d_ipl + al64(B * 4);
-    q->devhdr = zc && (k.flags & CNDP_MQ_F_DEVICE_HEADERS) && k.mode != CNDP_MQ_MAC_SWAP;
-    q->d_off = q->d_win + (zc ? B * 64 : 0);
-    q->d_len = q->d_off + (cnet && q->devhdr ? al64(B * 8) : 0);
-    q->d_md = q->d_len + (cnet && q->devhdr ? al64(B * 8) : 0);
-    q->d_bytes = cnet ? q->d_md + (q->devhdr ? al64(B * 8) : 0) : 64;
     r = -ENOMEM;
     if (hipStreamCreateWithFlags(&q->s, hipStreamNonBlocking) != hipSuccess)
         goto fail;
@@ -8515,7 +8553,7 @@ fail:
 
 extern "C" int cndp_gpu_mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, cndp_gpu_mq_t **out)
 {
-    return mq_create(c, conf, nullptr, nullptr, nullptr, out);
+    return mq_create(c, conf, MQ_BY_PLAIN, nullptr, nullptr, nullptr, out);
 }
 
 // cndp_mqfwd.h: the argument rules of the three cndpfwd modes, then the queue as for every mode
@@ -8525,7 +8563,8 @@ extern "C" int cndp_gpu_mq_create_fwd(cndp_gpu_ctx_t *c, const struct cndp_mq_co
     if (!c || !conf || !fwd || !out)
         return -EINVAL;
     *out = nullptr;
-    if (!mq_is_fwd(conf->mode) || conf->flags || conf->lport > 255u)
+    const MqMode *m = mq_mode(conf->mode, MQ_BY_FWD);
+    if (!m || (conf->flags & ~m->flags) || conf->lport > 255u)
         return -EINVAL;
     struct cndp_batch b0;
     memset(&b0, 0, sizeof(b0));
@@ -8550,7 +8589,7 @@ extern "C" int cndp_gpu_mq_create_fwd(cndp_gpu_ctx_t *c, const struct cndp_mq_co
         if (!built)
             return -ENOENT;
     }
-    return mq_create(c, conf, fwd, nullptr, nullptr, out);
+    return mq_create(c, conf, MQ_BY_FWD, fwd, nullptr, nullptr, out);
 }
 
 // cndp_mqcnet.h: cnet's ip4_forward node over a forwarding table
@@ -8560,12 +8599,13 @@ extern "C" int cndp_gpu_mq_create_ip4_forward(cndp_gpu_ctx_t *c, const struct cn
     if (!c || !conf || !tbl || !out)
         return -EINVAL;
     *out = nullptr;
-    if (conf->mode != CNDP_MQ_IP4_FORWARD || conf->flags)
+    const MqMode *m = mq_mode(conf->mode, MQ_BY_IPF);
+    if (!m || (conf->flags & ~m->flags))
         return -EINVAL;
     const int r = fwd_dev_check(tbl, c->dev); // one table, one device, as cndp_gpu_ip4_forward has it
     if (r)
         return r;
-    return mq_create(c, conf, nullptr, tbl, nullptr, out);
+    return mq_create(c, conf, MQ_BY_IPF, nullptr, tbl, nullptr, out);
 }
 
 // cndp_mql4.h: cnet's ip4_proto + udp_input nodes over a PCB table
@@ -8575,12 +8615,13 @@ extern "C" int cndp_gpu_mq_create_udp_input(cndp_gpu_ctx_t *c, const struct cndp
     if (!c || !conf || !tbl || !out)
         return -EINVAL;
     *out = nullptr;
-    if (conf->mode != CNDP_MQ_UDP_INPUT || conf->flags)
+    const MqMode *m = mq_mode(conf->mode, MQ_BY_UDP);
+    if (!m || (conf->flags & ~m->flags))
         return -EINVAL;
     const int r = pcb_dev_check(tbl, c->dev); // one table, one device, as cndp_gpu_udp_input has it
     if (r)
         return r;
-    return mq_create(c, conf, nullptr, nullptr, tbl, out);
+    return mq_create(c, conf, MQ_BY_UDP, nullptr, nullptr, tbl, out);
 }
 
 extern "C" void cndp_gpu_mq_free(cndp_gpu_mq_t *q)
@@ -8655,227 +8696,281 @@ static MqTables mq_tables(const cndp_gpu_ctx_t *c, const TblView &v4, const TblV
 
 static int rw_sync(cndp_gpu_ctx_t *c, hipStream_t s);
 
-static int mq_launch_kernels(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t slot_i)
+static inline uint32_t mq_grid(const MqSlot *sl) { return blocks_for(sl->n, MQ_TPB); }
+
+// CNDP_MQ_F_DEVICE_HEADERS: the kernel resolves frames in any of the queue's regions
+static void mq_args_regions(const cndp_gpu_mq_t *q, MqArgs &a)
 {
-    cndp_gpu_ctx_t *c = q->c;
-    int r = set_device(c->dev);
+    a.devhdr = 1;
+    a.nrg = (uint32_t)q->nrg;
+    for (int k = 0; k < q->nrg; k++) {
+        a.rg[k].host = (uint64_t)(uintptr_t)q->rg[k].host;
+        a.rg[k].len = q->rg[k].len;
+        a.rg[k].delta = q->rg[k].delta;
+    }
+}
+
+static int mq_launch_mac_swap(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    hipLaunchKernelGGL(k_mq_mac_swap, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a);
+    return 0;
+}
+
+static MqFwd mq_fwd_args(const cndp_gpu_mq_t *q)
+{
+    MqFwd w;
+    w.m0 = q->fwd.lport_mask[0];
+    w.m1 = q->fwd.lport_mask[1];
+    w.m2 = q->fwd.lport_mask[2];
+    w.m3 = q->fwd.lport_mask[3];
+    w.acl_mode = q->fwd.acl_mode;
+    w.acl_swap = q->fwd.acl_flags & CNDP_ACL_F_MAC_SWAP;
+    return w;
+}
+
+static int mq_launch_cfwd_fwd(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    hipLaunchKernelGGL(k_mq_cfwd<CNDP_CFWD_FWD>, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, mq_fwd_args(q),
+                       (const uint64_t *)nullptr, (const uint64_t *)nullptr);
+    return 0;
+}
+
+static int mq_launch_cfwd_l3fwd(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    // the FIB's mirror brought up to date on this stream, its view held until the launch
+    // is enqueued (as CNDP_MQ_IP4_LOOKUP does with the context's FIB)
+    struct cndp_tbl *t = &q->fwd.fib->t;
+    TblView v{};
+    const int r = tbl_acquire(t, q->s, &v);
     if (r)
         return r;
-    hipStream_t s = q->s;
-    const uint32_t n = sl->n;
-    const bool cnet = q->conf.mode == CNDP_MQ_CNET, zc = q->zc != 0;
+    if (!v.t24 || !v.t8) {
+        tbl_release(t);
+        return -EIO;
+    }
+    hipLaunchKernelGGL(k_mq_cfwd<CNDP_CFWD_L3FWD>, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, mq_fwd_args(q),
+                       (const uint64_t *)v.t24, (const uint64_t *)v.t8);
+    tbl_release(t);
+    return 0;
+}
+
+static int mq_launch_acl(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    // the ACL mirror's reader protocol: ordered after a reader on another stream, the
+    // image mirrored on this one, our end recorded for the next reader (acl_internal.h)
+    const uint32_t *img = nullptr;
+    int r = acl_dev_begin(q->fwd.acl, q->c->dev, q->s, &img, nullptr);
+    if (r)
+        return r; // -ENOENT: a failed build left no image
+    hipLaunchKernelGGL(k_mq_acl, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, mq_fwd_args(q), img);
+    const bool ok = hipGetLastError() == hipSuccess;
+    r = acl_dev_end(q->fwd.acl, q->s, ok);
+    return ok ? r : -EIO;
+}
+
+static int mq_launch_ipf(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    // the table's reader protocol (fwd_internal.h): ordered after a reader on another stream,
+    // the image and both FIBs mirrored on this one, the views held until the launch is enqueued
+    MqIpf w;
+    memset(&w, 0, sizeof(w));
+    int r = fwd_dev_begin(q->ipf, q->c->dev, q->s, &w.img, &w.arp, &w.rt);
+    if (r)
+        return r;
+    w.chunk = (const uint32_t *)(sl->hd + q->h_bst);
+    w.nch = sl->nb;
+    hipLaunchKernelGGL(k_mq_ip4_forward, dim3(sl->nb < 65536u ? sl->nb : 65536u), dim3(MQ_TPB), 0, q->s, a, w);
+    const bool ok = hipGetLastError() == hipSuccess;
+    r = fwd_dev_end(q->ipf, q->s, ok);
+    return ok ? r : -EIO;
+}
+
+static int mq_launch_udp(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    // the table's reader protocol (pcb_internal.h): ordered after a reader on another stream,
+    // the image mirrored on this one, our end recorded for the next reader
+    cndp_gpu_ctx_t *c = q->c;
+    const uint32_t *img = nullptr;
+    int r = pcb_dev_begin(q->pcb, c->dev, q->s, &img);
+    if (r)
+        return r;
+    // the table's lock is held between begin and end: img_words is the mirrored image's
+    const uint32_t lds = q->pcb->img_words * 4u;
+    if (c->tune_mq_pcb_lds && c->mq_pcb_lds_ok && lds <= MQ_UDP_LDS_MAX)
+        hipLaunchKernelGGL(k_mq_udp_input<true>, dim3(mq_grid(sl)), dim3(MQ_TPB), lds, q->s, a, img);
+    else
+        hipLaunchKernelGGL(k_mq_udp_input<false>, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, img);
+    const bool ok = hipGetLastError() == hipSuccess;
+    r = pcb_dev_end(q->pcb, q->s, ok);
+    return ok ? r : -EIO;
+}
+
+static int mq_launch_rewrite(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    const int r = rw_sync(q->c, q->s);
+    if (r)
+        return r;
+    a.rw = q->c->d_rw_tbl;
+    if (q->devhdr)
+        mq_args_regions(q, a);
+    hipLaunchKernelGGL(k_mq_ip4_rewrite, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a);
+    return 0;
+}
+
+static int mq_launch_lookup(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    cndp_gpu_ctx_t *c = q->c;
+    TblView v4{};
+    int r = tbl_acquire(&c->fib4->t, q->s, &v4);
+    if (r)
+        return r;
+    a.tb = mq_tables(c, v4, nullptr, 0);
+    a.rxparse = (q->conf.flags & CNDP_MQ_F_RX_PARSE) != 0;
+    const bool fuse = (q->conf.flags & CNDP_MQ_F_REWRITE) != 0;
+    if (fuse) {
+        if ((r = rw_sync(c, q->s))) {
+            tbl_release(&c->fib4->t);
+            return r;
+        }
+        a.rw = c->d_rw_tbl;
+        ((uint32_t *)(sl->h + q->h_bst))[sl->nb] = sl->n;
+        a.bstart = (const uint32_t *)(sl->hd + q->h_bst);
+    }
+    if (q->devhdr)
+        mq_args_regions(q, a);
+    if (fuse)
+        hipLaunchKernelGGL(k_mq_l3fwd_burst, dim3(sl->nb), dim3(MQ_L3_TPB), 0, q->s, a);
+    else
+        hipLaunchKernelGGL(k_mq_ip4_lookup, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a);
+    tbl_release(&c->fib4->t);
+    return 0;
+}
+
+// cnet device headers: the headers read on the device first (k_mq_cnet_hdr), the classify
+// and k_mq_cnet_post then take the frame offsets, lengths and metadata addresses it wrote
+static void mq_launch_cnet_hdr(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    const MqRegion &br = q->rg[sl->rg >= 0 ? sl->rg : 0];
+    a.devhdr = 1;
+    a.nrg = 1;
+    a.rg[0].host = (uint64_t)(uintptr_t)br.host;
+    a.rg[0].len = br.len;
+    a.rg[0].delta = br.delta;
+    a.w_off = (uint64_t *)(sl->d + q->d_off);
+    a.w_lens = (u32x2 *)(sl->d + q->d_len);
+    a.w_md = a.md ? (uint64_t *)(sl->d + q->d_md) : nullptr;
+    a.w_mdh = (uint64_t *)(sl->hd + q->h_md);
+    a.md_all = q->conf.metadata == nullptr;
+    a.n_pool = q->n_pool;
+    for (uint32_t k = 0; k < q->n_pool; k++)
+        a.md_pool[k] = q->pool[k];
+    hipLaunchKernelGGL(k_mq_cnet_hdr, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a);
+    a.off = a.w_off;
+    a.lens = a.w_lens;
+    a.md = a.w_md;
+}
+
+// one classify per run of equal-size graph bursts, the ptype node's speculation run with that
+// burst size, its state carried in the context from run to run and batch to batch
+static int mq_launch_cnet_runs(cndp_gpu_mq_t *q, MqSlot *sl, const MqArgs &a)
+{
+    cndp_gpu_ctx_t *c = q->c;
+    uint8_t *D = sl->d;
+    const uint32_t saved_B = c->spec_burst;
+    uint32_t i0 = 0;
+    int r = 0;
+    for (uint32_t k = 0; k < sl->nrun && !r; k++) {
+        struct cndp_batch b;
+        memset(&b, 0, sizeof(b));
+        b.mode = CNDP_MODE_CNET;
+        b.n = sl->run_n[k];
+        b.slab = a.slab;
+        b.slab_len = a.slab_len;
+        b.offsets = a.off + i0;
+        b.buf_len = sl->buf_len;
+        b.nh = (uint32_t *)(D + q->d_nh) + i0;
+        b.edge = D + q->d_edge + i0;
+        b.ptype = (uint32_t *)(D + q->d_pt) + i0;
+        b.rxmeta = (uint32_t *)(D + q->d_rm) + i0;
+        b.hash = a.want_hash ? (uint32_t *)(D + q->d_hash) + i0 : nullptr;
+        c->spec_burst = saved_B ? sl->run_B[k] : 0u;
+        c->mq_iplen = (uint32_t *)(D + q->d_ipl) + i0;
+        c->mq_win = a.md ? (u32x4 *)(D + q->d_win) + 4ull * i0 : nullptr;
+        r = classify_impl(c, &b, q->s, nullptr, nullptr); // a speculation error is the poll's (mq_poll)
+        c->mq_iplen = nullptr;
+        c->mq_win = nullptr;
+        i0 += sl->run_n[k];
+    }
+    c->spec_burst = saved_B;
+    return r;
+}
+
+static int mq_launch_cnet(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    cndp_gpu_ctx_t *c = q->c;
     uint8_t *HD = sl->hd, *D = sl->d;
+    const bool md = !(q->conf.flags & CNDP_MQ_F_NO_METADATA);
+    if (q->zc) { // frames as offsets in the batch's region, metadata written where it lies
+        const MqRegion &g = q->rg[sl->rg >= 0 ? sl->rg : 0];
+        a.slab = g.host + g.delta;
+        a.slab_len = g.len;
+        a.md = md ? (const uint64_t *)(HD + q->h_md) : nullptr;
+    }
+    a.rec_md = q->hostwb && md ? (u32x4 *)(HD + q->h_rmd) : nullptr;
+    if (q->devhdr)
+        mq_launch_cnet_hdr(q, sl, a);
+    int r = mq_launch_cnet_runs(q, sl, a);
+    if (r)
+        return r;
+    a.ptype = (const uint32_t *)(D + q->d_pt);
+    a.rxmeta = (const uint32_t *)(D + q->d_rm);
+    a.hash = (const uint32_t *)(D + q->d_hash);
+    a.edge8 = D + q->d_edge;
+    a.iplen = (uint32_t *)(D + q->d_ipl);
+    a.win = (const u32x4 *)(D + q->d_win);
+    TblView v4{}, v6{};
+    if ((r = tbl_acquire(&c->fib4->t, q->s, &v4)))
+        return r;
+    if ((r = tbl_acquire(&c->fib6->t, q->s, &v6))) {
+        tbl_release(&c->fib4->t);
+        return r;
+    }
+    a.tb = mq_tables(c, v4, &v6, sl->buf_len);
+    hipLaunchKernelGGL(k_mq_cnet_post, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a);
+    tbl_release(&c->fib4->t);
+    tbl_release(&c->fib6->t);
+    return 0;
+}
+
+// the arguments every mode's kernels take, then the mode's launch
+static int mq_launch_kernels(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t slot_i)
+{
+    int r = set_device(q->c->dev);
+    if (r)
+        return r;
+    uint8_t *HD = sl->hd;
     MqArgs a;
     memset(&a, 0, sizeof(a));
-    a.n = n;
-    a.zc = zc;
+    a.n = sl->n;
+    a.zc = q->zc != 0;
     a.mb = (const uint64_t *)(HD + q->h_mb);
     a.off = (const uint64_t *)(HD + q->h_off);
     a.lens = (const u32x2 *)(HD + q->h_len);
     a.priv = (const uint64_t *)(HD + q->h_len);
-    a.md = zc && cnet && !(q->conf.flags & CNDP_MQ_F_NO_METADATA) ? (const uint64_t *)(HD + q->h_md) : nullptr;
-    if (zc && cnet) {
-        const MqRegion &g = q->rg[sl->rg >= 0 ? sl->rg : 0];
-        a.slab = g.host + g.delta;
-        a.slab_len = g.len;
-    } else {
-        a.slab = HD + q->h_stage;
-        a.slab_len = sl->stage_used ? sl->stage_used : 64;
-    }
+    a.slab = HD + q->h_stage;
+    a.slab_len = sl->stage_used ? sl->stage_used : 64;
     a.edges = (uint16_t *)(HD + q->h_edge);
     a.priv1 = (uint64_t *)(HD + q->h_rec);
     a.rec = (u32x4 *)(HD + q->h_rec);
     a.hostwb = (uint32_t)q->hostwb;
-    a.rec_md = q->hostwb && cnet && !(q->conf.flags & CNDP_MQ_F_NO_METADATA) ? (u32x4 *)(HD + q->h_rmd) : nullptr;
     a.lport = q->conf.lport;
     a.want_hash = (q->conf.flags & CNDP_MQ_F_HASH) != 0;
     a.ticket = q->tickets + slot_i;
     a.flag = q->flags_d + slot_i * 16u;
     sl->seq = ++q->seq;
     a.seq = sl->seq;
-    const uint32_t g = blocks_for(n, MQ_TPB);
-    if (q->conf.mode == CNDP_MQ_MAC_SWAP) {
-        hipLaunchKernelGGL(k_mq_mac_swap, dim3(g), dim3(MQ_TPB), 0, s, a);
-    } else if (mq_is_fwd(q->conf.mode)) {
-        MqFwd w;
-        w.m0 = q->fwd.lport_mask[0];
-        w.m1 = q->fwd.lport_mask[1];
-        w.m2 = q->fwd.lport_mask[2];
-        w.m3 = q->fwd.lport_mask[3];
-        w.acl_mode = q->fwd.acl_mode;
-        w.acl_swap = q->fwd.acl_flags & CNDP_ACL_F_MAC_SWAP;
-        if (q->conf.mode == CNDP_MQ_CFWD_FWD) {
-            hipLaunchKernelGGL(k_mq_cfwd<CNDP_CFWD_FWD>, dim3(g), dim3(MQ_TPB), 0, s, a, w, (const uint64_t *)nullptr,
-                               (const uint64_t *)nullptr);
-        } else if (q->conf.mode == CNDP_MQ_CFWD_L3FWD) {
-            // the FIB's mirror brought up to date on this stream, its view held until the launch
-            // is enqueued (as CNDP_MQ_IP4_LOOKUP does with the context's FIB)
-            struct cndp_tbl *t = &q->fwd.fib->t;
-            TblView v{};
-            if ((r = tbl_acquire(t, s, &v)))
-                return r;
-            if (!v.t24 || !v.t8) {
-                tbl_release(t);
-                return -EIO;
-            }
-            hipLaunchKernelGGL(k_mq_cfwd<CNDP_CFWD_L3FWD>, dim3(g), dim3(MQ_TPB), 0, s, a, w, (const uint64_t *)v.t24,
-                               (const uint64_t *)v.t8);
-            tbl_release(t);
-        } else {
-            // the ACL mirror's reader protocol: ordered after a reader on another stream, the
-            // image mirrored on this one, our end recorded for the next reader (acl_internal.h)
-            const uint32_t *img = nullptr;
-            if ((r = acl_dev_begin(q->fwd.acl, c->dev, s, &img, nullptr)))
-                return r; // -ENOENT: a failed build left no image
-            hipLaunchKernelGGL(k_mq_acl, dim3(g), dim3(MQ_TPB), 0, s, a, w, img);
-            const bool ok = hipGetLastError() == hipSuccess;
-            r = acl_dev_end(q->fwd.acl, s, ok);
-            if (!ok || r)
-                return ok ? r : -EIO;
-        }
-    } else if (q->conf.mode == CNDP_MQ_IP4_FORWARD) {
-        // the table's reader protocol (fwd_internal.h): ordered after a reader on another stream,
-        // the image and both FIBs mirrored on this one, the views held until the launch is enqueued
-        MqIpf w;
-        memset(&w, 0, sizeof(w));
-        if ((r = fwd_dev_begin(q->ipf, c->dev, s, &w.img, &w.arp, &w.rt)))
-            return r;
-        w.chunk = (const uint32_t *)(HD + q->h_bst);
-        w.nch = sl->nb;
-        hipLaunchKernelGGL(k_mq_ip4_forward, dim3(sl->nb < 65536u ? sl->nb : 65536u), dim3(MQ_TPB), 0, s, a, w);
-        const bool ok = hipGetLastError() == hipSuccess;
-        r = fwd_dev_end(q->ipf, s, ok);
-        if (!ok || r)
-            return ok ? r : -EIO;
-    } else if (q->conf.mode == CNDP_MQ_UDP_INPUT) {
-        // the table's reader protocol (pcb_internal.h): ordered after a reader on another stream,
-        // the image mirrored on this one, our end recorded for the next reader
-        const uint32_t *img = nullptr;
-        if ((r = pcb_dev_begin(q->pcb, c->dev, s, &img)))
-            return r;
-        // the table's lock is held between begin and end: img_words is the mirrored image's
-        const uint32_t lds = q->pcb->img_words * 4u;
-        if (c->tune_mq_pcb_lds && c->mq_pcb_lds_ok && lds <= MQ_UDP_LDS_MAX)
-            hipLaunchKernelGGL(k_mq_udp_input<true>, dim3(g), dim3(MQ_TPB), lds, s, a, img);
-        else
-            hipLaunchKernelGGL(k_mq_udp_input<false>, dim3(g), dim3(MQ_TPB), 0, s, a, img);
-        const bool ok = hipGetLastError() == hipSuccess;
-        r = pcb_dev_end(q->pcb, s, ok);
-        if (!ok || r)
-            return ok ? r : -EIO;
-    } else if (q->conf.mode == CNDP_MQ_IP4_REWRITE) {
-        if ((r = rw_sync(c, s)))
-            return r;
-        a.rw = c->d_rw_tbl;
-        if (q->devhdr) { // frames in any registered region
-            a.devhdr = 1;
-            a.nrg = (uint32_t)q->nrg;
-            for (int k = 0; k < q->nrg; k++) {
-                a.rg[k].host = (uint64_t)(uintptr_t)q->rg[k].host;
-                a.rg[k].len = q->rg[k].len;
-                a.rg[k].delta = q->rg[k].delta;
-            }
-        }
-        hipLaunchKernelGGL(k_mq_ip4_rewrite, dim3(g), dim3(MQ_TPB), 0, s, a);
-    } else if (!cnet) {
-        TblView v4{};
-        if ((r = tbl_acquire(&c->fib4->t, s, &v4)))
-            return r;
-        a.tb = mq_tables(c, v4, nullptr, 0);
-        a.rxparse = (q->conf.flags & CNDP_MQ_F_RX_PARSE) != 0;
-        const bool fuse = (q->conf.flags & CNDP_MQ_F_REWRITE) != 0;
-        if (fuse) {
-            if ((r = rw_sync(c, s))) {
-                tbl_release(&c->fib4->t);
-                return r;
-            }
-            a.rw = c->d_rw_tbl;
-            ((uint32_t *)(sl->h + q->h_bst))[sl->nb] = n;
-            a.bstart = (const uint32_t *)(HD + q->h_bst);
-        }
-        if (q->devhdr) { // frames in any registered region
-            a.devhdr = 1;
-            a.nrg = (uint32_t)q->nrg;
-            for (int k = 0; k < q->nrg; k++) {
-                a.rg[k].host = (uint64_t)(uintptr_t)q->rg[k].host;
-                a.rg[k].len = q->rg[k].len;
-                a.rg[k].delta = q->rg[k].delta;
-            }
-        }
-        if (fuse)
-            hipLaunchKernelGGL(k_mq_l3fwd_burst, dim3(sl->nb), dim3(MQ_L3_TPB), 0, s, a);
-        else
-            hipLaunchKernelGGL(k_mq_ip4_lookup, dim3(g), dim3(MQ_TPB), 0, s, a);
-        tbl_release(&c->fib4->t);
-    } else {
-        // one classify per run of equal-size graph bursts, the ptype node's
-        // speculation run with that burst size, its state carried in the
-        // context from run to run and batch to batch
-        if (q->devhdr) { // the headers read on the device first (k_mq_cnet_hdr)
-            const MqRegion &br = q->rg[sl->rg >= 0 ? sl->rg : 0];
-            a.devhdr = 1;
-            a.nrg = 1;
-            a.rg[0].host = (uint64_t)(uintptr_t)br.host;
-            a.rg[0].len = br.len;
-            a.rg[0].delta = br.delta;
-            a.w_off = (uint64_t *)(D + q->d_off);
-            a.w_lens = (u32x2 *)(D + q->d_len);
-            a.w_md = a.md ? (uint64_t *)(D + q->d_md) : nullptr;
-            a.w_mdh = (uint64_t *)(HD + q->h_md);
-            a.md_all = q->conf.metadata == nullptr;
-            a.n_pool = q->n_pool;
-            for (uint32_t k = 0; k < q->n_pool; k++)
-                a.md_pool[k] = q->pool[k];
-            hipLaunchKernelGGL(k_mq_cnet_hdr, dim3(g), dim3(MQ_TPB), 0, s, a);
-            a.off = a.w_off;
-            a.lens = a.w_lens;
-            a.md = a.w_md;
-        }
-        const uint32_t saved_B = c->spec_burst;
-        uint32_t i0 = 0;
-        for (uint32_t k = 0; k < sl->nrun && !r; k++) {
-            struct cndp_batch b;
-            memset(&b, 0, sizeof(b));
-            b.mode = CNDP_MODE_CNET;
-            b.n = sl->run_n[k];
-            b.slab = a.slab;
-            b.slab_len = a.slab_len;
-            b.offsets = a.off + i0;
-            b.buf_len = sl->buf_len;
-            b.nh = (uint32_t *)(D + q->d_nh) + i0;
-            b.edge = D + q->d_edge + i0;
-            b.ptype = (uint32_t *)(D + q->d_pt) + i0;
-            b.rxmeta = (uint32_t *)(D + q->d_rm) + i0;
-            b.hash = a.want_hash ? (uint32_t *)(D + q->d_hash) + i0 : nullptr;
-            c->spec_burst = saved_B ? sl->run_B[k] : 0u;
-            c->mq_iplen = (uint32_t *)(D + q->d_ipl) + i0;
-            c->mq_win = a.md ? (u32x4 *)(D + q->d_win) + 4ull * i0 : nullptr;
-            r = classify_impl(c, &b, s, nullptr, nullptr); // a speculation error is the poll's (mq_poll)
-            c->mq_iplen = nullptr;
-            c->mq_win = nullptr;
-            i0 += sl->run_n[k];
-        }
-        c->spec_burst = saved_B;
-        if (r)
-            return r;
-        a.ptype = (const uint32_t *)(D + q->d_pt);
-        a.rxmeta = (const uint32_t *)(D + q->d_rm);
-        a.hash = (const uint32_t *)(D + q->d_hash);
-        a.edge8 = D + q->d_edge;
-        a.iplen = (uint32_t *)(D + q->d_ipl);
-        a.win = (const u32x4 *)(D + q->d_win);
-        TblView v4{}, v6{};
-        if ((r = tbl_acquire(&c->fib4->t, s, &v4)))
-            return r;
-        if ((r = tbl_acquire(&c->fib6->t, s, &v6))) {
-            tbl_release(&c->fib4->t);
-            return r;
-        }
-        a.tb = mq_tables(c, v4, &v6, sl->buf_len);
-        hipLaunchKernelGGL(k_mq_cnet_post, dim3(g), dim3(MQ_TPB), 0, s, a);
-        tbl_release(&c->fib4->t);
-        tbl_release(&c->fib6->t);
-    }
+    if ((r = q->mode->launch(q, sl, a)))
+        return r;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -8895,7 +8990,7 @@ static int mq_launch(cndp_gpu_mq_t *q)
         // the slot's staging: let them finish before its mbufs go back; the
         // speculation state they advanced part way restarts from 0
         (void)hipStreamSynchronize(q->s);
-        if (q->conf.mode == CNDP_MQ_CNET)
+        if (q->mode->spec)
             q->c->spec_reset = 1;
         sl->failed = 1;
         sl->state = MQ_DONE;
@@ -8906,8 +9001,8 @@ static int mq_launch(cndp_gpu_mq_t *q)
         sl->state = MQ_FLIGHT;
         q->in_flight++;
     }
-    q->n_batches++;
-    q->n_mbufs += sl->n;
+    q->n_stat[CNDP_MQ_STAT_BATCHES]++;
+    q->n_stat[CNDP_MQ_STAT_MBUFS] += sl->n;
     q->open = (q->open + 1) % q->conf.depth;
     return r;
 }
@@ -8947,162 +9042,292 @@ static void mq_learn_pool(cndp_gpu_mq_t *q, void *m)
     }
 }
 
-// one burst of k mbufs into the open slot sl (room checked by the caller)
-static void mq_fill(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+// the mbuf header fields every fill walk loads
+struct MqHdr {
+    uint8_t *m, *f;            // the mbuf, pktmbuf_mtod
+    uint16_t doff, blen, dlen; // data_off, buf_len, data_len
+    uint32_t room;             // the buffer's bytes from mtod on
+};
+
+static inline MqHdr mq_hdr(void *mbuf)
 {
-    const uint32_t mode = q->conf.mode;
-    const bool cnet = mode == CNDP_MQ_CNET, rw = mode == CNDP_MQ_IP4_REWRITE, zc = q->zc != 0;
-    const bool fw4 = mode == CNDP_MQ_IP4_FORWARD;
-    const bool want_md = cnet && zc && !(q->conf.flags & CNDP_MQ_F_NO_METADATA);
-    const bool devhdr = q->devhdr != 0;
-    uint8_t *H = sl->h;
-    uint64_t *hmb = (uint64_t *)(H + q->h_mb), *hoff = (uint64_t *)(H + q->h_off);
-    uint64_t *hlen = (uint64_t *)(H + q->h_len), *hmd = (uint64_t *)(H + q->h_md);
-    const uint32_t vec = k & ~3u; // ip4_rewrite: the 4-wide loop's share of the burst
-    if (devhdr) { // the kernels read the headers (CNDP_MQ_F_DEVICE_HEADERS): pointers only
-        // cnet: the default metadata (m + 64) must lie in the mbuf's region too
-        const uint64_t need = want_md ? 64u + 64u + MQ_MD_LEN : 64u;
-        if (want_md && q->conf.metadata && k)
-            mq_learn_pool(q, mbufs[0]);
-        for (uint32_t i = 0; i < k; i++) {
-            uint8_t *m = (uint8_t *)mbufs[i];
-            const int km = mq_region(q, m, need);
-            sl->mb[sl->n + i] = m;
-            hmb[sl->n + i] = km < 0 ? 0u : (uint64_t)(intptr_t)(m + q->rg[km].delta);
-            if (rw && km >= 0 && i >= vec) // ip4_rewrite's tail loop (bit 0: mbufs are 64-B aligned)
-                hmb[sl->n + i] |= MQ_RW_TAIL;
-            if (cnet && sl->rg < 0 && km >= 0) {
-                // the batch's region is its first frame's (as on the host-header
-                // path), which the host reads from that one header: mbuf headers
-                // may sit in another registered region than their buffers
-                const uint8_t *f = *(uint8_t *const *)(m + MB_BUF_ADDR) + *(const uint16_t *)(m + MB_DATA_OFF);
-                sl->rg = mq_region(q, f, 1);
-            }
-        }
-        return;
+    MqHdr h;
+    h.m = (uint8_t *)mbuf;
+    h.doff = *(const uint16_t *)(h.m + MB_DATA_OFF);
+    h.blen = *(const uint16_t *)(h.m + MB_BUF_LEN);
+    h.dlen = *(const uint16_t *)(h.m + MB_DATA_LEN);
+    h.room = h.blen > h.doff ? (uint32_t)(h.blen - h.doff) : 0u;
+    h.f = *(uint8_t *const *)(h.m + MB_BUF_ADDR) + h.doff;
+    return h;
+}
+
+// a fill walk's step to mbuf i of the burst: the mbuf headers MQ_PF ahead prefetched, and the frames
+// of the ones half as far (their buf_addr already in cache) where the host copies frame bytes
+static inline MqHdr mq_fill_next(MqSlot *sl, void *const *mbufs, uint32_t i, uint32_t k, bool zc)
+{
+    if (i + MQ_PF < k)
+        __builtin_prefetch((const uint8_t *)mbufs[i + MQ_PF], 1);
+    if (!zc && i + MQ_PF / 2 < k) {
+        const uint8_t *pm = (const uint8_t *)mbufs[i + MQ_PF / 2];
+        __builtin_prefetch(*(uint8_t *const *)(pm + MB_BUF_ADDR) + *(const uint16_t *)(pm + MB_DATA_OFF));
     }
+    sl->mb[sl->n + i] = mbufs[i];
+    return mq_hdr(mbufs[i]);
+}
+
+// zero-copy: the device address of mbuf m (0: outside every registered region)
+static inline uint64_t mq_mbuf_word(cndp_gpu_mq_t *q, uint8_t *m)
+{
+    const int km = mq_region(q, m, 64);
+    return km < 0 ? 0u : (uint64_t)(intptr_t)(m + q->rg[km].delta);
+}
+
+// staged: `want` bytes of the frame from byte `at` on (bounded by the buffer) into the next
+// `span` bytes of the slot's staging, zero-padded; mbuf j's offset there
+static inline void mq_stage(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t j, const MqHdr &h, uint32_t at, uint32_t want,
+                            uint64_t span)
+{
+    const uint32_t cp = h.room > at ? (h.room - at < want ? h.room - at : want) : 0u;
+    uint8_t *dst = sl->h + q->h_stage + sl->stage_used;
+    memcpy(dst, h.f + at, cp);
+    memset(dst + cp, 0, span - cp);
+    ((uint64_t *)(sl->h + q->h_off))[j] = sl->stage_used;
+    sl->stage_used += span;
+}
+
+static inline uint64_t al16(uint64_t x) { return (x + 15u) & ~15ull; }
+
+static void mq_fill_cnet(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    const bool zc = q->zc != 0, want_md = zc && !(q->conf.flags & CNDP_MQ_F_NO_METADATA);
+    uint64_t *hmb = (uint64_t *)(sl->h + q->h_mb), *hoff = (uint64_t *)(sl->h + q->h_off);
+    uint64_t *hmd = (uint64_t *)(sl->h + q->h_md);
+    u32x2 *hlen = (u32x2 *)(sl->h + q->h_len);
     for (uint32_t i = 0; i < k; i++) {
-        // the mbuf headers MQ_PF ahead, the frames of the ones half as far
-        // (their buf_addr already in cache) where the host copies frame bytes
-        if (i + MQ_PF < k)
-            __builtin_prefetch((const uint8_t *)mbufs[i + MQ_PF], 1);
-        if (!zc && i + MQ_PF / 2 < k) {
-            const uint8_t *pm = (const uint8_t *)mbufs[i + MQ_PF / 2];
-            __builtin_prefetch(*(uint8_t *const *)(pm + MB_BUF_ADDR) + *(const uint16_t *)(pm + MB_DATA_OFF));
-        }
-        uint8_t *m = (uint8_t *)mbufs[i];
-        uint8_t *buf = *(uint8_t *const *)(m + MB_BUF_ADDR);
-        const uint16_t doff = *(const uint16_t *)(m + MB_DATA_OFF);
-        const uint16_t blen = *(const uint16_t *)(m + MB_BUF_LEN);
-        const uint16_t dlen = *(const uint16_t *)(m + MB_DATA_LEN);
-        const uint32_t room = blen > doff ? (uint32_t)(blen - doff) : 0u;
         const uint32_t j = sl->n + i;
-        uint8_t *f = buf + doff; // pktmbuf_mtod
-        sl->mb[j] = m;
-        if (mode == CNDP_MQ_UDP_INPUT) {
-            // the readable bytes: data_len clipped at the buffer's end, then at the frame's
-            // region's end (zero-copy) or at stage_max (staged, copied into a 16-byte-aligned,
-            // zero-padded place of the staging); front / back: what an aligned load may overhang
-            const uint32_t l3 = (uint32_t)((*(const uint64_t *)(m + MB_TX_OFFLOAD) >> 7) & 0x1FFu);
-            uint64_t R = dlen < room ? dlen : room, front = 0, back;
-            if (zc) {
-                const int kf = mq_region(q, m, 64) < 0 ? -1 : mq_region(q, f, 1);
-                if (kf < 0) {
-                    hoff[j] = hlen[j] = 0; // not taken
-                    continue;
-                }
-                const MqRegion &g = q->rg[kf];
-                const uint64_t in_front = (uint64_t)(f - g.host), left = g.len - in_front;
-                R = R < left ? R : left;
-                front = in_front < 15u ? in_front : 15u;
-                back = left - R < 15u ? left - R : 15u;
-                hoff[j] = (uint64_t)(intptr_t)(f + g.delta);
-            } else {
-                R = R < q->conf.stage_max ? R : q->conf.stage_max;
-                const uint64_t span = R > 16u ? (R + 15u) & ~15ull : 16u;
-                uint8_t *dst = H + q->h_stage + sl->stage_used;
-                memcpy(dst, f, R);
-                memset(dst + R, 0, span - R);
-                back = span - R < 15u ? span - R : 15u;
-                hoff[j] = sl->stage_used;
-                sl->stage_used += span;
-            }
-            hlen[j] = l3 | R << MQ_UDP_R_SHIFT | front << MQ_UDP_FRONT_SHIFT | back << MQ_UDP_BACK_SHIFT;
-            continue;
-        }
-        if (cnet) {
-            u32x2 l;
-            l.x = (uint32_t)dlen | (room << 16);
-            l.y = (uint32_t)blen | ((uint32_t)doff << 16);
-            ((u32x2 *)hlen)[j] = l;
-        }
-        if (rw) {
-            hmb[j] = i >= vec ? MQ_RW_TAIL : 0u;
-            hlen[j] = *(const uint64_t *)(m + MB_UDATA64); // node_mbuf_priv1
-        }
-        if (mode == CNDP_MQ_ACL_FWD)
-            hlen[j] = dlen; // validate_ipv4_pkt's link-length test
-        uint32_t l2 = 0;
-        if (fw4) { // m->l2_len, and whether pktmbuf_adjust(m, -l2_len) takes place (l2_len <= data_off)
-            l2 = (uint32_t)(*(const uint64_t *)(m + MB_TX_OFFLOAD) & 0x7Fu);
-            hlen[j] = l2 | (l2 <= doff ? MQ_IPF_ADJ : 0u);
-        }
+        const MqHdr h = mq_fill_next(sl, mbufs, i, k, zc);
+        u32x2 l;
+        l.x = (uint32_t)h.dlen | (h.room << 16);
+        l.y = (uint32_t)h.blen | ((uint32_t)h.doff << 16);
+        hlen[j] = l;
         if (zc) {
-            if (!rw) {
-                const int km = mq_region(q, m, 64);
-                hmb[j] = km < 0 ? 0u : (uint64_t)(intptr_t)(m + q->rg[km].delta);
-            }
-            if (mq_is_fwd(mode)) { // the kernels look at the frame word alone: none for an mbuf outside
-                hoff[j] = hmb[j] ? mq_frame_word(q, f) : 0u;
-            } else if (fw4) {
-                // the frame word of the IPv4 header, and how many of the l2_len bytes in front of
-                // it lie in its region (rg_last after mq_frame_word): the MAC bytes go there
-                hoff[j] = hmb[j] ? mq_frame_word(q, f) : 0u;
-                if (hoff[j]) {
-                    const uint64_t in_front = (uint64_t)(f - q->rg[q->rg_last].host);
-                    hlen[j] |= (uint64_t)(in_front < l2 ? (uint32_t)in_front : l2) << 8;
-                }
-            } else if (cnet) {
-                // frame offset in the batch's region (the first frame's);
-                // outside it: the region's end, which reads as zero bytes
-                const int kf = mq_region(q, f, 1);
-                if (sl->rg < 0 && kf >= 0)
-                    sl->rg = kf;
-                const MqRegion &g = q->rg[sl->rg >= 0 ? sl->rg : 0];
-                hoff[j] = kf >= 0 && kf == sl->rg ? (uint64_t)(f - g.host) : g.len;
-                if (want_md) {
-                    uint8_t *md = mq_md_host(q, m);
-                    const int kd = md ? mq_region(q, md, MQ_MD_LEN) : -1;
-                    hmd[j] = kd < 0 ? 0u : (uint64_t)(intptr_t)(md + q->rg[kd].delta);
-                }
-            } else {
-                hoff[j] = mq_frame_word(q, f);
+            hmb[j] = mq_mbuf_word(q, h.m);
+            // frame offset in the batch's region (the first frame's);
+            // outside it: the region's end, which reads as zero bytes
+            const int kf = mq_region(q, h.f, 1);
+            if (sl->rg < 0 && kf >= 0)
+                sl->rg = kf;
+            const MqRegion &g = q->rg[sl->rg >= 0 ? sl->rg : 0];
+            hoff[j] = kf >= 0 && kf == sl->rg ? (uint64_t)(h.f - g.host) : g.len;
+            if (want_md) {
+                uint8_t *md = mq_md_host(q, h.m);
+                const int kd = md ? mq_region(q, md, MQ_MD_LEN) : -1;
+                hmd[j] = kd < 0 ? 0u : (uint64_t)(intptr_t)(md + q->rg[kd].delta);
             }
         } else {
             // staged copy of the bytes the nodes can read (bounded by the buffer)
-            uint32_t at = 0, want;
-            if (cnet) {
-                const uint32_t cap = q->conf.stage_max > MQ_SHORT && mq_short_reach(f, room) ? MQ_SHORT
-                                                                                             : q->conf.stage_max;
-                want = room < cap ? room : cap;
-            } else if (mode == CNDP_MQ_IP4_LOOKUP) {
-                const bool rxp = (q->conf.flags & CNDP_MQ_F_RX_PARSE) != 0;
-                at = rxp ? MQ_W4R_AT : MQ_W4_AT;
-                want = rxp ? MQ_W4R : MQ_W4;
-            } else if (fw4) { // header bytes 8-19: TTL, checksum, destination
-                at = 8;
-                want = 12;
-            } else {
-                want = q->stage;
+            const uint32_t cap = q->conf.stage_max > MQ_SHORT && mq_short_reach(h.f, h.room) ? MQ_SHORT
+                                                                                           : q->conf.stage_max;
+            const uint32_t want = h.room < cap ? h.room : cap;
+            mq_stage(q, sl, j, h, 0, want, al64(want ? want : 1));
+        }
+    }
+}
+
+// the modes whose kernels take a frame and nothing of its header (ip4_lookup, mac swap, cndpfwd fwd /
+// l3fwd; acl: data_len too, for validate_ipv4_pkt's link-length test); staged: `want` bytes from
+// byte `at` on; gate: the kernels look at the frame word alone, so there is none for an mbuf outside
+static inline void mq_fill_frames(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k, bool gate, bool len,
+                                  uint32_t at, uint32_t want)
+{
+    const bool zc = q->zc != 0;
+    uint64_t *hmb = (uint64_t *)(sl->h + q->h_mb), *hoff = (uint64_t *)(sl->h + q->h_off);
+    uint64_t *hlen = (uint64_t *)(sl->h + q->h_len);
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t j = sl->n + i;
+        const MqHdr h = mq_fill_next(sl, mbufs, i, k, zc);
+        if (len)
+            hlen[j] = h.dlen;
+        if (zc) {
+            hmb[j] = mq_mbuf_word(q, h.m);
+            hoff[j] = !gate || hmb[j] ? mq_frame_word(q, h.f) : 0u;
+        } else {
+            mq_stage(q, sl, j, h, at, want, al16(want));
+        }
+    }
+}
+
+static void mq_fill_lookup(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mb, uint32_t k)
+{
+    if (q->conf.flags & CNDP_MQ_F_RX_PARSE) // the ethertype too
+        mq_fill_frames(q, sl, mb, k, false, false, MQ_W4R_AT, MQ_W4R);
+    else
+        mq_fill_frames(q, sl, mb, k, false, false, MQ_W4_AT, MQ_W4);
+}
+static void mq_fill_mac_swap(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mb, uint32_t k) { mq_fill_frames(q, sl, mb, k, false, false, 0, q->stage); }
+static void mq_fill_cfwd(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mb, uint32_t k) { mq_fill_frames(q, sl, mb, k, true, false, 0, q->stage); }
+static void mq_fill_acl(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mb, uint32_t k) { mq_fill_frames(q, sl, mb, k, true, true, 0, q->stage); }
+
+static void mq_fill_rewrite(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    const bool zc = q->zc != 0;
+    const uint32_t vec = k & ~3u; // the 4-wide loop's share of the burst
+    uint64_t *hmb = (uint64_t *)(sl->h + q->h_mb), *hoff = (uint64_t *)(sl->h + q->h_off);
+    uint64_t *hlen = (uint64_t *)(sl->h + q->h_len);
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t j = sl->n + i;
+        const MqHdr h = mq_fill_next(sl, mbufs, i, k, zc);
+        hmb[j] = i >= vec ? MQ_RW_TAIL : 0u;
+        hlen[j] = *(const uint64_t *)(h.m + MB_UDATA64); // node_mbuf_priv1
+        if (zc)
+            hoff[j] = mq_frame_word(q, h.f);
+        else
+            mq_stage(q, sl, j, h, 0, q->stage, al16(q->stage));
+    }
+}
+
+static void mq_fill_ipf(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    const bool zc = q->zc != 0;
+    uint64_t *hmb = (uint64_t *)(sl->h + q->h_mb), *hoff = (uint64_t *)(sl->h + q->h_off);
+    uint64_t *hlen = (uint64_t *)(sl->h + q->h_len);
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t j = sl->n + i;
+        const MqHdr h = mq_fill_next(sl, mbufs, i, k, zc);
+        // m->l2_len, and whether pktmbuf_adjust(m, -l2_len) takes place (l2_len <= data_off)
+        const uint32_t l2 = (uint32_t)(*(const uint64_t *)(h.m + MB_TX_OFFLOAD) & 0x7Fu);
+        hlen[j] = l2 | (l2 <= h.doff ? MQ_IPF_ADJ : 0u);
+        if (zc) {
+            // the frame word of the IPv4 header, and how many of the l2_len bytes in front of
+            // it lie in its region (rg_last after mq_frame_word): the MAC bytes go there
+            hmb[j] = mq_mbuf_word(q, h.m);
+            hoff[j] = hmb[j] ? mq_frame_word(q, h.f) : 0u;
+            if (hoff[j]) {
+                const uint64_t in_front = (uint64_t)(h.f - q->rg[q->rg_last].host);
+                hlen[j] |= (uint64_t)(in_front < l2 ? (uint32_t)in_front : l2) << 8;
             }
-            const uint32_t cp = room > at ? (room - at < want ? room - at : want) : 0u;
-            uint8_t *dst = H + q->h_stage + sl->stage_used;
-            memcpy(dst, f + at, cp);
-            const uint64_t span = cnet ? al64(want ? want : 1) : fw4 ? (uint64_t)MQ_IPF_STAGE : (uint64_t)((want + 15u) & ~15u);
-            memset(dst + cp, 0, span - cp);
+        } else {
+            mq_stage(q, sl, j, h, 8, 12, MQ_IPF_STAGE); // header bytes 8-19: TTL, checksum, destination
+        }
+    }
+}
+
+// the readable bytes: data_len clipped at the buffer's end, then at the frame's
+// region's end (zero-copy) or at stage_max (staged, copied into a 16-byte-aligned,
+// zero-padded place of the staging); front / back: what an aligned load may overhang
+static void mq_fill_udp(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    const bool zc = q->zc != 0;
+    uint64_t *hoff = (uint64_t *)(sl->h + q->h_off), *hlen = (uint64_t *)(sl->h + q->h_len);
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t j = sl->n + i;
+        const MqHdr h = mq_fill_next(sl, mbufs, i, k, zc);
+        const uint32_t l3 = (uint32_t)((*(const uint64_t *)(h.m + MB_TX_OFFLOAD) >> 7) & 0x1FFu);
+        uint64_t R = h.dlen < h.room ? h.dlen : h.room, front = 0, back;
+        if (zc) {
+            const int kf = mq_region(q, h.m, 64) < 0 ? -1 : mq_region(q, h.f, 1);
+            if (kf < 0) {
+                hoff[j] = hlen[j] = 0; // not taken
+                continue;
+            }
+            const MqRegion &g = q->rg[kf];
+            const uint64_t in_front = (uint64_t)(h.f - g.host), left = g.len - in_front;
+            R = R < left ? R : left;
+            front = in_front < 15u ? in_front : 15u;
+            back = left - R < 15u ? left - R : 15u;
+            hoff[j] = (uint64_t)(intptr_t)(h.f + g.delta);
+        } else {
+            R = R < q->conf.stage_max ? R : q->conf.stage_max;
+            const uint64_t span = R > 16u ? al16(R) : 16u;
+            uint8_t *dst = sl->h + q->h_stage + sl->stage_used;
+            memcpy(dst, h.f, R);
+            memset(dst + R, 0, span - R);
+            back = span - R < 15u ? span - R : 15u;
             hoff[j] = sl->stage_used;
             sl->stage_used += span;
         }
+        hlen[j] = l3 | R << MQ_UDP_R_SHIFT | front << MQ_UDP_FRONT_SHIFT | back << MQ_UDP_BACK_SHIFT;
+    }
+}
+
+// CNDP_MQ_F_DEVICE_HEADERS: the kernels read the headers, the host hands over pointers only
+static void mq_fill_devhdr(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    uint64_t *hmb = (uint64_t *)(sl->h + q->h_mb);
+    for (uint32_t i = 0; i < k; i++) {
+        sl->mb[sl->n + i] = mbufs[i];
+        hmb[sl->n + i] = mq_mbuf_word(q, (uint8_t *)mbufs[i]);
+    }
+}
+
+// ip4_rewrite: the tail loop's mbufs marked (bit 0: mbufs are 64-B aligned)
+static void mq_fill_devhdr_rewrite(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    uint64_t *hmb = (uint64_t *)(sl->h + q->h_mb);
+    mq_fill_devhdr(q, sl, mbufs, k);
+    for (uint32_t i = k & ~3u; i < k; i++)
+        if (hmb[sl->n + i])
+            hmb[sl->n + i] |= MQ_RW_TAIL;
+}
+
+// cnet: the default metadata (m + 64) must lie in the mbuf's region too; the batch's region is
+// its first frame's (as on the host-header path), which the host reads from that one header:
+// mbuf headers may sit in another registered region than their buffers
+static void mq_fill_devhdr_cnet(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    const bool want_md = !(q->conf.flags & CNDP_MQ_F_NO_METADATA);
+    const uint64_t need = want_md ? 64u + 64u + MQ_MD_LEN : 64u;
+    uint64_t *hmb = (uint64_t *)(sl->h + q->h_mb);
+    if (want_md && q->conf.metadata && k)
+        mq_learn_pool(q, mbufs[0]);
+    for (uint32_t i = 0; i < k; i++) {
+        uint8_t *m = (uint8_t *)mbufs[i];
+        const int km = mq_region(q, m, need);
+        sl->mb[sl->n + i] = m;
+        hmb[sl->n + i] = km < 0 ? 0u : (uint64_t)(intptr_t)(m + q->rg[km].delta);
+        if (sl->rg < 0 && km >= 0)
+            sl->rg = mq_region(q, mq_hdr(m).f, 1);
+    }
+}
+
+// CNDP_MQ_F_REWRITE: this burst's first mbuf (the kernel's block)
+static void mq_burst_lookup(cndp_gpu_mq_t *q, MqSlot *sl, void *const *, uint32_t)
+{
+    if (q->conf.flags & CNDP_MQ_F_REWRITE)
+        ((uint32_t *)(sl->h + q->h_bst))[sl->nb++] = sl->n;
+}
+
+// this burst's chunks of 64 (k_mq_ip4_forward's waves)
+static void mq_burst_ipf(cndp_gpu_mq_t *q, MqSlot *sl, void *const *, uint32_t k)
+{
+    for (uint32_t c0 = 0; c0 < k; c0 += MQ_TPB)
+        ((uint32_t *)(sl->h + q->h_bst))[sl->nb++] =
+            (sl->n + c0) | ((k - c0 < MQ_TPB ? k - c0 : MQ_TPB) << MQ_IPF_CNT_SHIFT);
+}
+
+// cnet: MQ_RUNS_MAX runs, and a burst of k would start another
+static bool mq_no_room_cnet(const MqSlot *sl, uint32_t k)
+{
+    return sl->nrun == MQ_RUNS_MAX && !(sl->run_closed == 0 && k <= sl->run_B[sl->nrun - 1]);
+}
+
+static void mq_burst_cnet(cndp_gpu_mq_t *, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    // the batch's buf_len for the input nodes' length test; frames with
+    // another one are re-evaluated by k_mq_cnet_post
+    if (sl->n == 0)
+        sl->buf_len = *(const uint16_t *)((const uint8_t *)mbufs[0] + MB_BUF_LEN);
+    // runs of equal-size bursts, each closed by a shorter one
+    if (sl->nrun && !sl->run_closed && k == sl->run_B[sl->nrun - 1]) {
+        sl->run_n[sl->nrun - 1] += k;
+    } else if (sl->nrun && !sl->run_closed && k < sl->run_B[sl->nrun - 1]) {
+        sl->run_n[sl->nrun - 1] += k;
+        sl->run_closed = 1;
+    } else {
+        sl->run_B[sl->nrun] = k;
+        sl->run_n[sl->nrun] = k;
+        sl->nrun++;
+        sl->run_closed = 0;
     }
 }
 
@@ -9115,7 +9340,7 @@ extern "C" int cndp_gpu_mq_submit(cndp_gpu_mq_t *q, void *const *mbufs, uint32_t
         q->err = 0;
         return e;
     }
-    const bool cnet = q->conf.mode == CNDP_MQ_CNET;
+    const MqMode *m = q->mode;
     uint32_t done = 0;
     while (done < n) {
         MqSlot *sl = mq_open_slot(q);
@@ -9123,10 +9348,7 @@ extern "C" int cndp_gpu_mq_submit(cndp_gpu_mq_t *q, void *const *mbufs, uint32_t
             break;
         // one graph burst (<= 256 mbufs) at a time, never split across batches
         const uint32_t k = n - done < MQ_BURST ? n - done : MQ_BURST;
-        bool full = sl->n + k > q->conf.batch;
-        if (cnet && !full && sl->nrun == MQ_RUNS_MAX && !(sl->run_closed == 0 && k <= sl->run_B[sl->nrun - 1]))
-            full = true;
-        if (full) {
+        if (sl->n + k > q->conf.batch || (m->no_room && m->no_room(sl, k))) {
             const int r = mq_launch(q);
             if (r) {
                 if (done)
@@ -9135,33 +9357,11 @@ extern "C" int cndp_gpu_mq_submit(cndp_gpu_mq_t *q, void *const *mbufs, uint32_t
             }
             continue;
         }
-        if (sl->n == 0) {
+        if (sl->n == 0)
             sl->t_open_ns = now_ns();
-            // the batch's buf_len for the input nodes' length test; frames with
-            // another one are re-evaluated by k_mq_cnet_post
-            if (cnet)
-                sl->buf_len = *(const uint16_t *)((const uint8_t *)mbufs[done] + MB_BUF_LEN);
-        }
-        if (q->conf.flags & CNDP_MQ_F_REWRITE) // this burst's first mbuf (the kernel's block)
-            ((uint32_t *)(sl->h + q->h_bst))[sl->nb++] = sl->n;
-        if (q->conf.mode == CNDP_MQ_IP4_FORWARD) // this burst's chunks of 64 (k_mq_ip4_forward's waves)
-            for (uint32_t c0 = 0; c0 < k; c0 += MQ_TPB)
-                ((uint32_t *)(sl->h + q->h_bst))[sl->nb++] =
-                    (sl->n + c0) | ((k - c0 < MQ_TPB ? k - c0 : MQ_TPB) << MQ_IPF_CNT_SHIFT);
-        mq_fill(q, sl, mbufs + done, k);
-        if (cnet) { // runs of equal-size bursts, each closed by a shorter one
-            if (sl->nrun && !sl->run_closed && k == sl->run_B[sl->nrun - 1]) {
-                sl->run_n[sl->nrun - 1] += k;
-            } else if (sl->nrun && !sl->run_closed && k < sl->run_B[sl->nrun - 1]) {
-                sl->run_n[sl->nrun - 1] += k;
-                sl->run_closed = 1;
-            } else {
-                sl->run_B[sl->nrun] = k;
-                sl->run_n[sl->nrun] = k;
-                sl->nrun++;
-                sl->run_closed = 0;
-            }
-        }
+        if (m->burst)
+            m->burst(q, sl, mbufs + done, k);
+        q->fill(q, sl, mbufs + done, k);
         sl->n += k;
         done += k;
         q->pending += k;
@@ -9177,209 +9377,144 @@ extern "C" int cndp_gpu_mq_submit(cndp_gpu_mq_t *q, void *const *mbufs, uint32_t
 }
 
 // ipv4/ipv6_save_metadata on the host (ip4_input.c:33-48, ip6_input.c:32-48)
-// from the frame at the input node's mtod
-static void mq_save_md_host(uint8_t *md, const uint8_t *ip, bool v6)
+// from the header's two addresses
+static inline void mq_save_md_addrs(uint8_t *md, const uint8_t *src, const uint8_t *dst, bool v6)
 {
     const uint8_t fam = v6 ? (uint8_t)MQ_AF_INET6 : (uint8_t)MQ_AF_INET, alen = v6 ? 16 : 4;
     md[0] = md[20] = fam;
     md[1] = md[21] = alen;
-    memcpy(md + 4, ip + (v6 ? 8 : 12), alen);
-    memcpy(md + 24, ip + (v6 ? 24 : 16), alen);
+    memcpy(md + 4, src, alen);
+    memcpy(md + 24, dst, alen);
 }
 
-// one finished slot's results into its mbufs where the kernels did not
-// write them (staged: every field; zero-copy cnet: metadata the device could
-// not reach; zero-copy with host writeback: every field, from records)
-static void mq_writeback(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
+// the same from the frame at the input node's mtod
+static inline void mq_save_md_host(uint8_t *md, const uint8_t *ip, bool v6)
 {
-    const uint32_t mode = q->conf.mode;
+    mq_save_md_addrs(md, ip + (v6 ? 8 : 12), ip + (v6 ? 24 : 16), v6);
+}
+
+// The writebacks: mbufs [i0, i1) of a finished slot get the results the kernels did not write
+// into them (staged: every field; zero-copy cnet: metadata the device could not reach; zero-copy
+// with host writeback: every field, from records).
+
+// udp_input: every edit of the two nodes from the device's records, zero-copy or staged
+// (pcb_udp_apply, pcb_internal.h: the text the host twin runs), and the six counters
+static void mq_wb_udp(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
+{
+    const u32x4 *rec = (const u32x4 *)(sl->h + q->h_rec);
+    uint16_t *edw = (uint16_t *)(sl->h + q->h_edge);
+    for (uint32_t i = i0; i < i1; i++) {
+        if (i + MQ_PF < i1)
+            __builtin_prefetch(sl->mb[i + MQ_PF], 1);
+        const uint32_t e = edw[i];
+        if (e == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
+            continue;
+        if ((e >> 8) == CNDP_MQ_NODE_IP4_PROTO) {
+            q->n_stat[(e & 0xFFu) == CNDP_IP4_PROTO_TCP ? CNDP_MQ_STAT_L4_TCP : CNDP_MQ_STAT_L4_PROTO_DROP]++;
+            continue;
+        }
+        uint8_t *m = (uint8_t *)sl->mb[i];
+        uint8_t *md = mq_md_host(q, m);
+        if (!md) { // udp_input.c:57-59
+            edw[i] = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_PKT_DROP);
+            q->n_stat[CNDP_MQ_STAT_L4_NOMD]++;
+            continue;
+        }
+        const u32x4 r = rec[i];
+        const uint32_t idx = r.x >> 16;
+        const bool recv = e == CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_CHNL_RECV);
+        uint64_t user = 0;
+        if (recv && idx < q->pcb->max) // a value set while the batch was in flight may or may not show
+            user = __atomic_load_n(&q->pcb->user[idx], __ATOMIC_RELAXED);
+        pcb_udp_apply(m, md, e, user, r.y, r.z, r.w);
+        q->n_stat[recv                          ? CNDP_MQ_STAT_L4_RECV
+                  : (e & CNDP_MQ_EDGE_L4_CKSUM) ? CNDP_MQ_STAT_L4_CKSUM
+                                                : CNDP_MQ_STAT_L4_NOMATCH]++;
+    }
+}
+
+// ip4_forward: pktmbuf_adjust(m, -l2_len) on the host, zero-copy or staged; staged also the frame
+// bytes, in the reference's order: TTL / checksum at the old mtod, then the MAC bytes at
+// the new one (which win where l2_len < 12 makes them overlap), each below buf_len
+static void mq_wb_ipf(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
+{
     const uint16_t *ed = (const uint16_t *)(sl->h + q->h_edge);
-    if (mode == CNDP_MQ_UDP_INPUT) {
-        // every edit of the two nodes from the device's records, zero-copy or staged
-        // (pcb_udp_apply, pcb_internal.h: the text the host twin runs), and the six counters
-        const u32x4 *rec = (const u32x4 *)(sl->h + q->h_rec);
-        uint16_t *edw = (uint16_t *)(sl->h + q->h_edge);
-        for (uint32_t i = i0; i < i1; i++) {
-            if (i + MQ_PF < i1)
-                __builtin_prefetch(sl->mb[i + MQ_PF], 1);
-            const uint32_t e = edw[i];
-            if (e == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
-                continue;
-            if ((e >> 8) == CNDP_MQ_NODE_IP4_PROTO) {
-                q->n_l4[(e & 0xFFu) == CNDP_IP4_PROTO_TCP ? CNDP_MQ_STAT_L4_TCP - CNDP_MQ_STAT_L4_RECV
-                                                          : CNDP_MQ_STAT_L4_PROTO_DROP - CNDP_MQ_STAT_L4_RECV]++;
-                continue;
-            }
-            uint8_t *m = (uint8_t *)sl->mb[i];
-            uint8_t *md = mq_md_host(q, m);
-            if (!md) { // udp_input.c:57-59
-                edw[i] = CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_PKT_DROP);
-                q->n_l4[CNDP_MQ_STAT_L4_NOMD - CNDP_MQ_STAT_L4_RECV]++;
-                continue;
-            }
-            const u32x4 r = rec[i];
-            const uint32_t idx = r.x >> 16;
-            const bool recv = e == CNDP_MQ_EDGE(CNDP_MQ_NODE_UDP_INPUT, CNDP_UDP_INPUT_CHNL_RECV);
-            uint64_t user = 0;
-            if (recv && idx < q->pcb->max) // a value set while the batch was in flight may or may not show
-                user = __atomic_load_n(&q->pcb->user[idx], __ATOMIC_RELAXED);
-            pcb_udp_apply(m, md, e, user, r.y, r.z, r.w);
-            q->n_l4[recv                          ? 0
-                    : (e & CNDP_MQ_EDGE_L4_CKSUM) ? CNDP_MQ_STAT_L4_CKSUM - CNDP_MQ_STAT_L4_RECV
-                                                  : CNDP_MQ_STAT_L4_NOMATCH - CNDP_MQ_STAT_L4_RECV]++;
-        }
-        return;
-    }
-    if (mode == CNDP_MQ_IP4_FORWARD) {
-        // pktmbuf_adjust(m, -l2_len) on the host, zero-copy or staged; staged also the frame
-        // bytes, in the reference's order: TTL / checksum at the old mtod, then the MAC bytes at
-        // the new one (which win where l2_len < 12 makes them overlap), each below buf_len
-        const uint64_t *hl = (const uint64_t *)(sl->h + q->h_len), *ho = (const uint64_t *)(sl->h + q->h_off);
-        for (uint32_t i = i0; i < i1; i++) {
-            if (i + MQ_PF < i1)
-                __builtin_prefetch(sl->mb[i + MQ_PF], 1);
-            if (ed[i] == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
-                continue;
-            uint8_t *m = (uint8_t *)sl->mb[i];
-            const uint16_t doff = *(const uint16_t *)(m + MB_DATA_OFF);
-            const uint16_t l2 = (uint16_t)(hl[i] & 0x7Fu);
-            const bool adj = (hl[i] & MQ_IPF_ADJ) != 0;
-            if (!q->zc) {
-                uint8_t *buf = *(uint8_t **)(m + MB_BUF_ADDR);
-                const uint16_t blen = *(const uint16_t *)(m + MB_BUF_LEN);
-                const uint8_t *st = sl->h + q->h_stage + ho[i];
-                if ((uint32_t)doff + 8u < blen)
-                    buf[doff + 8u] = st[0];
-                for (uint32_t j = 10; j < 12; j++)
-                    if ((uint32_t)doff + j < blen)
-                        buf[doff + j] = st[j - 8u];
-                if (adj && (ed[i] & CNDP_MQ_EDGE_FWD_MASK) != CNDP_FWD_EDGE_ARP_REQUEST) {
-                    const uint32_t e0 = (uint32_t)doff - l2;
-                    for (uint32_t j = 0; j < 12; j++)
-                        if (e0 + j < blen)
-                            buf[e0 + j] = st[16u + j];
-                }
-            }
-            if (adj) {
-                *(uint16_t *)(m + MB_DATA_OFF) = (uint16_t)(doff - l2);
-                *(uint16_t *)(m + MB_DATA_LEN) = (uint16_t)(*(const uint16_t *)(m + MB_DATA_LEN) + l2);
-            }
-        }
-        return;
-    }
-    if (mode == CNDP_MQ_IP4_LOOKUP && (q->hostwb || !q->zc)) {
-        // node_mbuf_priv1 (ip4_lookup.c:144-154) and, with the soft parse,
-        // packet_type: staged from the staged ethertype, host writeback from
-        // the record (pkt_cls's drops carry their packet_type there)
-        const uint64_t *priv1 = (const uint64_t *)(sl->h + q->h_rec);
-        const uint64_t *ho = (const uint64_t *)(sl->h + q->h_off);
-        const bool rxp = (q->conf.flags & CNDP_MQ_F_RX_PARSE) != 0;
-        for (uint32_t i = i0; i < i1; i++) {
-            if (i + MQ_PF < i1)
-                __builtin_prefetch((uint8_t *)sl->mb[i + MQ_PF] + MB_UDATA64, 1);
-            if (ed[i] == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
-                continue;
-            uint8_t *m = (uint8_t *)sl->mb[i];
-            const bool cls_drop = ed[i] == CNDP_MQ_EDGE_CLS_DROP;
-            if (rxp) {
-                uint32_t pt;
-                if (q->hostwb) {
-                    pt = cls_drop ? (uint32_t)priv1[i] : 0x90u;
-                } else {
-                    const uint8_t *e = sl->h + q->h_stage + ho[i];
-                    const uint32_t et = ((uint32_t)e[0] << 8) | e[1];
-                    pt = et == 0x0800u ? 0x90u : et == 0x86DDu ? 0xE0u : 0u;
-                }
-                *(uint32_t *)(m + MB_PTYPE) = pt;
-                if (cls_drop) // pkt_cls dropped it: ip4_lookup never saw it
-                    continue;
-            }
-            *(uint64_t *)(m + MB_UDATA64) = priv1[i];
-        }
-        return;
-    }
-    if (q->hostwb) {
-        const uint32_t *rec = (const uint32_t *)(sl->h + q->h_rec);
-        const uint8_t *rmd = sl->h + q->h_rmd;
-        const bool wh = (q->conf.flags & CNDP_MQ_F_HASH) != 0;
-        const bool md_on = !(q->conf.flags & CNDP_MQ_F_NO_METADATA);
-        const uint16_t lport = q->conf.lport;
-        for (uint32_t i = i0; i < i1; i++) {
-            if (i + MQ_PF < i1)
-                __builtin_prefetch(sl->mb[i + MQ_PF], 1);
-            if (ed[i] == MQ_EDGE_NONE) // outside every registered region: untouched
-                continue;
-            uint8_t *m = (uint8_t *)sl->mb[i];
-            const uint32_t pt = rec[4 * i], rm = rec[4 * i + 1], w2 = rec[4 * i + 2];
-            // eth_rx mbuf_update (eth_rx.c:35-63), then the input node's data_len
-            *(uint32_t *)(m + MB_PTYPE) = pt;
-            *(uint64_t *)(m + MB_OL_FLAGS) = (uint64_t)(rm >> 29) << 61;
-            *(uint64_t *)(m + MB_TX_OFFLOAD) = (uint64_t)(rm & 0xffffffu);
-            *(uint16_t *)(m + MB_LPORT) = lport;
-            const uint16_t l2 = (uint16_t)(rm & 0x7fu);
-            uint16_t doff = *(uint16_t *)(m + MB_DATA_OFF);
-            const uint16_t dlen0 = *(uint16_t *)(m + MB_DATA_LEN);
-            const uint16_t blen = *(const uint16_t *)(m + MB_BUF_LEN);
-            if (l2 <= dlen0 && (uint32_t)l2 + doff <= blen) // pktmbuf_adj_offset
-                *(uint16_t *)(m + MB_DATA_OFF) = (uint16_t)(doff + l2);
-            *(uint16_t *)(m + MB_DATA_LEN) = (uint16_t)(w2 & 0xffffu);
-            if (wh)
-                *(uint32_t *)(m + MB_HASH) = rec[4 * i + 3];
-            const uint32_t node = w2 >> 24;
-            if (md_on && (node == CNDP_MQ_NODE_IP4 || node == CNDP_MQ_NODE_IP6)) {
-                uint8_t *md = mq_md_host(q, m);
-                if (md) { // ipv4/ipv6_save_metadata (ip4_input.c:33-48, ip6_input.c:32-48)
-                    const bool v6 = node == CNDP_MQ_NODE_IP6;
-                    const uint8_t fam = v6 ? (uint8_t)MQ_AF_INET6 : (uint8_t)MQ_AF_INET, alen = v6 ? 16 : 4;
-                    md[0] = md[20] = fam;
-                    md[1] = md[21] = alen;
-                    memcpy(md + 4, rmd + 32ull * i, alen);
-                    memcpy(md + 24, rmd + 32ull * i + 16, alen);
-                }
-            }
-        }
-        return;
-    }
-    if (q->zc) {
-        if (mode != CNDP_MQ_CNET || (q->conf.flags & CNDP_MQ_F_NO_METADATA))
-            return;
-        const uint64_t *hmd = (const uint64_t *)(sl->h + q->h_md);
-        for (uint32_t i = i0; i < i1; i++) {
-            const uint32_t node = ed[i] >> 8;
-            if (hmd[i] || ed[i] == MQ_EDGE_NONE || (node != CNDP_MQ_NODE_IP4 && node != CNDP_MQ_NODE_IP6))
-                continue;
-            uint8_t *m = (uint8_t *)sl->mb[i], *md = mq_md_host(q, m);
-            if (md) // the mbuf fields are final: mtod is the input node's
-                mq_save_md_host(md, *(uint8_t **)(m + MB_BUF_ADDR) + *(const uint16_t *)(m + MB_DATA_OFF),
-                                node == CNDP_MQ_NODE_IP6);
-        }
-        return;
-    }
-    const uint8_t *R = sl->h + q->h_rec;
-    const uint64_t *ho = (const uint64_t *)(sl->h + q->h_off);
-    if (mode == CNDP_MQ_MAC_SWAP || mode == CNDP_MQ_IP4_REWRITE || mq_is_fwd(mode)) { // the changed bytes back into the frame
-        // cndpfwd modes: fwd bytes 0-11, l3fwd up to byte 25, acl bytes 0-11 of the frames it
-        // forwarded (edge = a port) and only with the swap flag
-        const bool acl = mode == CNDP_MQ_ACL_FWD;
-        const uint32_t span = mode == CNDP_MQ_MAC_SWAP || mode == CNDP_MQ_CFWD_FWD ? 12u
-                            : mode == CNDP_MQ_CFWD_L3FWD                          ? 26u
-                            : acl ? ((q->fwd.acl_flags & CNDP_ACL_F_MAC_SWAP) ? 12u : 0u)
-                                  : MQ_RW_STAGE;
-        if (!span)
-            return;
-        for (uint32_t i = i0; i < i1; i++) {
-            if (acl && ed[i] > 255u)
-                continue;
-            uint8_t *m = (uint8_t *)sl->mb[i];
+    const uint64_t *hl = (const uint64_t *)(sl->h + q->h_len), *ho = (const uint64_t *)(sl->h + q->h_off);
+    for (uint32_t i = i0; i < i1; i++) {
+        if (i + MQ_PF < i1)
+            __builtin_prefetch(sl->mb[i + MQ_PF], 1);
+        if (ed[i] == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
+            continue;
+        uint8_t *m = (uint8_t *)sl->mb[i];
+        const uint16_t doff = *(const uint16_t *)(m + MB_DATA_OFF);
+        const uint16_t l2 = (uint16_t)(hl[i] & 0x7Fu);
+        const bool adj = (hl[i] & MQ_IPF_ADJ) != 0;
+        if (!q->zc) {
             uint8_t *buf = *(uint8_t **)(m + MB_BUF_ADDR);
-            const uint16_t doff = *(const uint16_t *)(m + MB_DATA_OFF);
             const uint16_t blen = *(const uint16_t *)(m + MB_BUF_LEN);
-            const uint32_t room = blen > doff ? (uint32_t)(blen - doff) : 0u;
-            memcpy(buf + doff, sl->h + q->h_stage + ho[i], room < span ? room : span);
+            const uint8_t *st = sl->h + q->h_stage + ho[i];
+            if ((uint32_t)doff + 8u < blen)
+                buf[doff + 8u] = st[0];
+            for (uint32_t j = 10; j < 12; j++)
+                if ((uint32_t)doff + j < blen)
+                    buf[doff + j] = st[j - 8u];
+            if (adj && (ed[i] & CNDP_MQ_EDGE_FWD_MASK) != CNDP_FWD_EDGE_ARP_REQUEST) {
+                const uint32_t e0 = (uint32_t)doff - l2;
+                for (uint32_t j = 0; j < 12; j++)
+                    if (e0 + j < blen)
+                        buf[e0 + j] = st[16u + j];
+            }
         }
-        return;
+        if (adj) {
+            *(uint16_t *)(m + MB_DATA_OFF) = (uint16_t)(doff - l2);
+            *(uint16_t *)(m + MB_DATA_LEN) = (uint16_t)(*(const uint16_t *)(m + MB_DATA_LEN) + l2);
+        }
     }
-    const uint32_t *rec = (const uint32_t *)R;
+}
+
+// ip4_lookup, staged or with host writeback: node_mbuf_priv1 (ip4_lookup.c:144-154) and,
+// with the soft parse, packet_type: staged from the staged ethertype, host writeback from
+// the record (pkt_cls's drops carry their packet_type there)
+static void mq_wb_lookup(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
+{
+    const uint16_t *ed = (const uint16_t *)(sl->h + q->h_edge);
+    const uint64_t *priv1 = (const uint64_t *)(sl->h + q->h_rec);
+    const uint64_t *ho = (const uint64_t *)(sl->h + q->h_off);
+    const bool rxp = (q->conf.flags & CNDP_MQ_F_RX_PARSE) != 0;
+    for (uint32_t i = i0; i < i1; i++) {
+        if (i + MQ_PF < i1)
+            __builtin_prefetch((uint8_t *)sl->mb[i + MQ_PF] + MB_UDATA64, 1);
+        if (ed[i] == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
+            continue;
+        uint8_t *m = (uint8_t *)sl->mb[i];
+        const bool cls_drop = ed[i] == CNDP_MQ_EDGE_CLS_DROP;
+        if (rxp) {
+            uint32_t pt;
+            if (q->hostwb) {
+                pt = cls_drop ? (uint32_t)priv1[i] : 0x90u;
+            } else {
+                const uint8_t *e = sl->h + q->h_stage + ho[i];
+                const uint32_t et = ((uint32_t)e[0] << 8) | e[1];
+                pt = et == 0x0800u ? 0x90u : et == 0x86DDu ? 0xE0u : 0u;
+            }
+            *(uint32_t *)(m + MB_PTYPE) = pt;
+            if (cls_drop) // pkt_cls dropped it: ip4_lookup never saw it
+                continue;
+        }
+        *(uint64_t *)(m + MB_UDATA64) = priv1[i];
+    }
+}
+
+// cnet, staged or with host writeback: every field from the records.  The metadata's addresses
+// come from the records' second half (host: host writeback, the frames stay unread), else from
+// the staged copy of the frame (read in sequence, not the frame's own line again), where the
+// IP header sits where the adjusted data_off put it
+static inline void mq_wb_cnet_records(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1, bool host)
+{
+    const uint16_t *ed = (const uint16_t *)(sl->h + q->h_edge);
+    const uint32_t *rec = (const uint32_t *)(sl->h + q->h_rec);
+    const uint8_t *rmd = sl->h + q->h_rmd, *stage = sl->h + q->h_stage;
+    const uint64_t *ho = (const uint64_t *)(sl->h + q->h_off);
     const u32x2 *lens = (const u32x2 *)(sl->h + q->h_len); // data_off at submit (staging offset 0)
     const bool wh = (q->conf.flags & CNDP_MQ_F_HASH) != 0;
     const bool md_on = !(q->conf.flags & CNDP_MQ_F_NO_METADATA);
@@ -9387,9 +9522,11 @@ static void mq_writeback(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
     for (uint32_t i = i0; i < i1; i++) {
         if (i + MQ_PF < i1)
             __builtin_prefetch(sl->mb[i + MQ_PF], 1);
+        if (host && ed[i] == MQ_EDGE_NONE) // outside every registered region: untouched
+            continue;
         uint8_t *m = (uint8_t *)sl->mb[i];
         const uint32_t pt = rec[4 * i], rm = rec[4 * i + 1], w2 = rec[4 * i + 2];
-        // eth_rx mbuf_update (eth_rx.c:35-63)
+        // eth_rx mbuf_update (eth_rx.c:35-63), then the input node's data_len
         *(uint32_t *)(m + MB_PTYPE) = pt;
         *(uint64_t *)(m + MB_OL_FLAGS) = (uint64_t)(rm >> 29) << 61;
         *(uint64_t *)(m + MB_TX_OFFLOAD) = (uint64_t)(rm & 0xffffffu);
@@ -9406,48 +9543,137 @@ static void mq_writeback(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
             *(uint32_t *)(m + MB_HASH) = rec[4 * i + 3];
         const uint32_t node = w2 >> 24;
         if (md_on && (node == CNDP_MQ_NODE_IP4 || node == CNDP_MQ_NODE_IP6)) {
-            // the addresses from the staged copy of the frame (read in
-            // sequence, not the frame's own line again); the IP header sits
-            // where the adjusted data_off put it
             uint8_t *md = mq_md_host(q, m);
-            const uint8_t *st = sl->h + q->h_stage + ((const uint64_t *)(sl->h + q->h_off))[i];
-            if (md)
-                mq_save_md_host(md, st + (doff - (uint16_t)(lens[i].y >> 16)),
-                                node == CNDP_MQ_NODE_IP6);
+            if (!md)
+                continue;
+            if (host)
+                mq_save_md_addrs(md, rmd + 32ull * i, rmd + 32ull * i + 16, node == CNDP_MQ_NODE_IP6);
+            else
+                mq_save_md_host(md, stage + ho[i] + (doff - (uint16_t)(lens[i].y >> 16)), node == CNDP_MQ_NODE_IP6);
         }
     }
 }
 
-// cndpfwd modes: the reference loops' counters by CNDP_MQ_STAT_* key, from the
-// edges of k mbufs (CNDP_MQ_EDGE_NONE counts nowhere)
-static void mq_count_fwd(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
+static void mq_wb_cnet_host(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1) { mq_wb_cnet_records(q, sl, i0, i1, true); }
+static void mq_wb_cnet_staged(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1) { mq_wb_cnet_records(q, sl, i0, i1, false); }
+
+// cnet zero-copy: the metadata the device could not reach (no device address at h_md)
+static void mq_wb_cnet_zc(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
 {
-    const bool acl = q->conf.mode == CNDP_MQ_ACL_FWD;
-    for (uint32_t i = 0; i < k; i++) {
-        const uint32_t e = ed[i];
-        if (e == MQ_EDGE_NONE)
+    if (q->conf.flags & CNDP_MQ_F_NO_METADATA)
+        return;
+    const uint16_t *ed = (const uint16_t *)(sl->h + q->h_edge);
+    const uint64_t *hmd = (const uint64_t *)(sl->h + q->h_md);
+    for (uint32_t i = i0; i < i1; i++) {
+        const uint32_t node = ed[i] >> 8;
+        if (hmd[i] || ed[i] == MQ_EDGE_NONE || (node != CNDP_MQ_NODE_IP4 && node != CNDP_MQ_NODE_IP6))
             continue;
-        if (!acl)
-            q->n_fwd[(e & CNDP_MQ_EDGE_ECHO) ? CNDP_MQ_STAT_ECHO : CNDP_MQ_STAT_FORWARD]++;
-        else
-            q->n_fwd[e == CNDP_MQ_EDGE_ACL_PREFILTER ? CNDP_MQ_STAT_ACL_PREFILTER
-                     : e == CNDP_MQ_EDGE_ACL_DENY    ? CNDP_MQ_STAT_ACL_DENY
-                                                     : CNDP_MQ_STAT_ACL_PERMIT]++;
+        uint8_t *m = (uint8_t *)sl->mb[i], *md = mq_md_host(q, m);
+        if (md) // the mbuf fields are final: mtod is the input node's
+            mq_save_md_host(md, *(uint8_t **)(m + MB_BUF_ADDR) + *(const uint16_t *)(m + MB_DATA_OFF),
+                            node == CNDP_MQ_NODE_IP6);
     }
 }
 
-// ip4_forward mode: the node's three outcomes from the edges of k mbufs
-// (CNDP_MQ_EDGE_NONE counts nowhere)
+// staged modes that edit frames: the mode's first wb_span staged bytes back into the frame
+// (bounded by the buffer); ports_only: of the frames whose edge is a port
+static inline void mq_wb_span(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1, bool ports_only)
+{
+    const uint16_t *ed = (const uint16_t *)(sl->h + q->h_edge);
+    const uint64_t *ho = (const uint64_t *)(sl->h + q->h_off);
+    const uint32_t span = q->mode->wb_span;
+    for (uint32_t i = i0; i < i1; i++) {
+        if (ports_only && ed[i] > 255u)
+            continue;
+        const MqHdr h = mq_hdr(sl->mb[i]);
+        memcpy(h.f, sl->h + q->h_stage + ho[i], h.room < span ? h.room : span);
+    }
+}
+
+static void mq_wb_frames(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1) { mq_wb_span(q, sl, i0, i1, false); }
+
+static void mq_wb_acl(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
+{
+    if (q->fwd.acl_flags & CNDP_ACL_F_MAC_SWAP) // only the frames it forwarded, and only with the swap flag
+        mq_wb_span(q, sl, i0, i1, true);
+}
+
+// The counters poll keeps from the edges of the k mbufs it hands back (CNDP_MQ_EDGE_NONE
+// counts nowhere): cndpfwd's loops, acl_fwd_test's, ip4_forward's three outcomes
+static void mq_count_cfwd(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
+{
+    for (uint32_t i = 0; i < k; i++)
+        if (ed[i] != MQ_EDGE_NONE)
+            q->n_stat[(ed[i] & CNDP_MQ_EDGE_ECHO) ? CNDP_MQ_STAT_ECHO : CNDP_MQ_STAT_FORWARD]++;
+}
+
+static void mq_count_acl(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
+{
+    for (uint32_t i = 0; i < k; i++)
+        if (ed[i] != MQ_EDGE_NONE)
+            q->n_stat[ed[i] == CNDP_MQ_EDGE_ACL_PREFILTER ? CNDP_MQ_STAT_ACL_PREFILTER
+                      : ed[i] == CNDP_MQ_EDGE_ACL_DENY    ? CNDP_MQ_STAT_ACL_DENY
+                                                          : CNDP_MQ_STAT_ACL_PERMIT]++;
+}
+
 static void mq_count_ipf(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
 {
-    for (uint32_t i = 0; i < k; i++) {
-        const uint32_t e = ed[i];
-        if (e == MQ_EDGE_NONE)
-            continue;
-        q->n_ipf[(e & CNDP_MQ_EDGE_FWD_GATEWAY)                                 ? CNDP_FWD_STAT_GATEWAY
-                 : (e & CNDP_MQ_EDGE_FWD_MASK) == CNDP_FWD_EDGE_ARP_REQUEST ? CNDP_FWD_STAT_ARP_REQUEST
-                                                                            : CNDP_FWD_STAT_DIRECT]++;
-    }
+    for (uint32_t i = 0; i < k; i++)
+        if (ed[i] != MQ_EDGE_NONE)
+            q->n_stat[(ed[i] & CNDP_MQ_EDGE_FWD_GATEWAY)                                 ? CNDP_MQ_STAT_FWD_GATEWAY
+                      : (ed[i] & CNDP_MQ_EDGE_FWD_MASK) == CNDP_FWD_EDGE_ARP_REQUEST ? CNDP_MQ_STAT_FWD_ARP_REQUEST
+                                                                                     : CNDP_MQ_STAT_FWD_DIRECT]++;
+}
+
+static uint32_t mq_stage_lookup(const struct cndp_mq_conf *k) { return (k->flags & CNDP_MQ_F_RX_PARSE) ? 32u : MQ_W4; }
+static uint32_t mq_stage_cnet(const struct cndp_mq_conf *k) { return (uint32_t)al64(k->stage_max); }
+// at most: a frame takes its readable bytes rounded up to 16
+static uint32_t mq_stage_udp(const struct cndp_mq_conf *k) { return (k->stage_max + 15u) & ~15u; }
+
+#define MQ_F_NODE (CNDP_MQ_F_HASH | CNDP_MQ_F_NO_METADATA | CNDP_MQ_F_DEVICE_HEADERS) // every node mode takes these
+static const MqMode mq_modes[] = {
+    {.mode = CNDP_MQ_IP4_LOOKUP, .by = MQ_BY_PLAIN,
+     .flags = MQ_F_NODE | CNDP_MQ_F_RX_PARSE | CNDP_MQ_F_REWRITE | CNDP_MQ_F_HOST_WRITEBACK, .fibs = MQ_FIB4,
+     .stage_of = mq_stage_lookup, .rec = 8, .bst_flag = CNDP_MQ_F_REWRITE,
+     .fill = mq_fill_lookup, .fill_devhdr = mq_fill_devhdr, .burst = mq_burst_lookup, .launch = mq_launch_lookup,
+     .wb_staged = mq_wb_lookup, .wb_host = mq_wb_lookup},
+    {.mode = CNDP_MQ_CNET, .by = MQ_BY_PLAIN, .flags = MQ_F_NODE | CNDP_MQ_F_HOST_WRITEBACK,
+     .fibs = MQ_FIB4 | MQ_FIB6, .wb_hdr = true,
+     .stage_of = mq_stage_cnet, .len = true, .rec = 16, .md = true, .dev_out = true, .spec = true,
+     .fill = mq_fill_cnet, .fill_devhdr = mq_fill_devhdr_cnet, .no_room = mq_no_room_cnet, .burst = mq_burst_cnet,
+     .launch = mq_launch_cnet, .wb_zc = mq_wb_cnet_zc, .wb_staged = mq_wb_cnet_staged, .wb_host = mq_wb_cnet_host},
+    {.mode = CNDP_MQ_MAC_SWAP, .by = MQ_BY_PLAIN, .flags = MQ_F_NODE, // the flags mean nothing to it
+     .stage = MQ_SWAP, .wb_span = 12,
+     .fill = mq_fill_mac_swap, .launch = mq_launch_mac_swap, .wb_staged = mq_wb_frames},
+    {.mode = CNDP_MQ_IP4_REWRITE, .by = MQ_BY_PLAIN, .flags = MQ_F_NODE,
+     .stage = MQ_RW_STAGE, .wb_span = MQ_RW_STAGE, .len = true,
+     .fill = mq_fill_rewrite, .fill_devhdr = mq_fill_devhdr_rewrite, .launch = mq_launch_rewrite,
+     .wb_staged = mq_wb_frames},
+    {.mode = CNDP_MQ_CFWD_FWD, .by = MQ_BY_FWD,
+     .stage = MQ_SWAP, .wb_span = 12, .stat_lo = CNDP_MQ_STAT_FORWARD, .stat_hi = CNDP_MQ_STAT_ECHO,
+     .fill = mq_fill_cfwd, .launch = mq_launch_cfwd_fwd, .wb_staged = mq_wb_frames, .count = mq_count_cfwd},
+    {.mode = CNDP_MQ_CFWD_L3FWD, .by = MQ_BY_FWD,
+     .stage = MQ_FWD_STAGE, .wb_span = 26, .stat_lo = CNDP_MQ_STAT_FORWARD, .stat_hi = CNDP_MQ_STAT_ECHO,
+     .fill = mq_fill_cfwd, .launch = mq_launch_cfwd_l3fwd, .wb_staged = mq_wb_frames, .count = mq_count_cfwd},
+    {.mode = CNDP_MQ_ACL_FWD, .by = MQ_BY_FWD,
+     .stage = MQ_FWD_STAGE, .wb_span = 12, .len = true, .stat_lo = CNDP_MQ_STAT_ACL_PREFILTER, .stat_hi = CNDP_MQ_STAT_ACL_PERMIT,
+     .fill = mq_fill_acl, .launch = mq_launch_acl, .wb_staged = mq_wb_acl, .count = mq_count_acl},
+    {.mode = CNDP_MQ_IP4_FORWARD, .by = MQ_BY_IPF,
+     .stage = MQ_IPF_STAGE, .len = true, .bst = true,
+     .stat_lo = CNDP_MQ_STAT_FWD_DIRECT, .stat_hi = CNDP_MQ_STAT_FWD_ARP_REQUEST,
+     .fill = mq_fill_ipf, .burst = mq_burst_ipf, .launch = mq_launch_ipf, .wb_zc = mq_wb_ipf, .wb_staged = mq_wb_ipf,
+     .count = mq_count_ipf},
+    // its counters are kept by its writeback, where the no-metadata outcome is decided
+    {.mode = CNDP_MQ_UDP_INPUT, .by = MQ_BY_UDP,
+     .stage_of = mq_stage_udp, .len = true, .rec = 16, .rec_zc = true,
+     .stat_lo = CNDP_MQ_STAT_L4_RECV, .stat_hi = CNDP_MQ_STAT_L4_NOMD,
+     .fill = mq_fill_udp, .launch = mq_launch_udp, .wb_zc = mq_wb_udp, .wb_staged = mq_wb_udp},
+};
+
+static const MqMode *mq_mode(uint32_t mode, uint32_t by)
+{
+    const uint32_t n = sizeof(mq_modes) / sizeof(mq_modes[0]);
+    return mode < n && mq_modes[mode].mode == mode && mq_modes[mode].by == by ? &mq_modes[mode] : nullptr;
 }
 
 extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, uint32_t max)
@@ -9483,7 +9709,7 @@ extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges,
             // a speculation wait of this batch expired (its flag was raised
             // after k_spec_fallback's error store): its edges are not the
             // node's, so it comes back like a failed launch
-            if (q->conf.mode == CNDP_MQ_CNET && spec_err_take(q->c)) {
+            if (q->mode->spec && spec_err_take(q->c)) {
                 sl->failed = 1;
                 uint16_t *ed = (uint16_t *)(sl->h + q->h_edge);
                 for (uint32_t i = 0; i < sl->n; i++)
@@ -9494,14 +9720,12 @@ extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges,
         if (sl->state != MQ_DONE)
             break;
         const uint32_t take = sl->n - sl->polled < max - got ? sl->n - sl->polled : max - got;
-        if (!sl->failed)
-            mq_writeback(q, sl, sl->polled, sl->polled + take);
+        if (!sl->failed && q->writeback)
+            q->writeback(q, sl, sl->polled, sl->polled + take);
         memcpy(mbufs + got, sl->mb + sl->polled, (size_t)take * sizeof(void *));
         memcpy(edges + got, (const uint16_t *)(sl->h + q->h_edge) + sl->polled, (size_t)take * 2);
-        if (mq_is_fwd(q->conf.mode)) // cndp_mqfwd.h: the counters, from the edges handed back
-            mq_count_fwd(q, edges + got, take);
-        if (q->conf.mode == CNDP_MQ_IP4_FORWARD) // cndp_mqcnet.h
-            mq_count_ipf(q, edges + got, take);
+        if (q->mode->count) // the mode's counters, from the edges handed back
+            q->mode->count(q, edges + got, take);
         sl->polled += take;
         got += take;
         q->pending -= take;
@@ -9513,41 +9737,19 @@ extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges,
     return (int)got;
 }
 
+// Batches, mbufs and the cndpfwd and ip4_forward families answer on every mode (0 where the mode
+// does not count them).  The keys of a family added later are known only to the mode that counts
+// them: on every other mode they stay the unknown keys they were before that mode existed.
+static_assert(CNDP_MQ_STAT_BATCHES == 1 && CNDP_MQ_STAT_FWD_ARP_REQUEST == 10 && CNDP_MQ_STAT_L4_RECV == 11 &&
+                  CNDP_MQ_STAT_L4_NOMD == 16,
+              "cndp_gpu_mq_stat's key ranges");
 extern "C" int64_t cndp_gpu_mq_stat(const cndp_gpu_mq_t *q, int key)
 {
-    if (!q)
+    if (!q || key < CNDP_MQ_STAT_BATCHES || key > CNDP_MQ_STAT_L4_NOMD)
         return -EINVAL;
-    switch (key) {
-    case CNDP_MQ_STAT_BATCHES:
-        return (int64_t)q->n_batches;
-    case CNDP_MQ_STAT_MBUFS:
-        return (int64_t)q->n_mbufs;
-    case CNDP_MQ_STAT_FORWARD: // cndp_mqfwd.h; a key of another mode's family stays 0
-    case CNDP_MQ_STAT_ECHO:
-    case CNDP_MQ_STAT_ACL_PREFILTER:
-    case CNDP_MQ_STAT_ACL_DENY:
-    case CNDP_MQ_STAT_ACL_PERMIT:
-        return (int64_t)q->n_fwd[key];
-    case CNDP_MQ_STAT_FWD_DIRECT: // cndp_mqcnet.h
-        return (int64_t)q->n_ipf[CNDP_FWD_STAT_DIRECT];
-    case CNDP_MQ_STAT_FWD_GATEWAY:
-        return (int64_t)q->n_ipf[CNDP_FWD_STAT_GATEWAY];
-    case CNDP_MQ_STAT_FWD_ARP_REQUEST:
-        return (int64_t)q->n_ipf[CNDP_FWD_STAT_ARP_REQUEST];
-    case CNDP_MQ_STAT_L4_RECV: // cndp_mql4.h
-    case CNDP_MQ_STAT_L4_NOMATCH:
-    case CNDP_MQ_STAT_L4_CKSUM:
-    case CNDP_MQ_STAT_L4_PROTO_DROP:
-    case CNDP_MQ_STAT_L4_TCP:
-    case CNDP_MQ_STAT_L4_NOMD:
-        // known to a CNDP_MQ_UDP_INPUT queue only: on every other mode these keys stay the
-        // unknown keys they were before the mode existed
-        if (q->conf.mode != CNDP_MQ_UDP_INPUT)
-            return -EINVAL;
-        return (int64_t)q->n_l4[key - CNDP_MQ_STAT_L4_RECV];
-    default:
-        return -EINVAL;
-    }
+    if (key <= CNDP_MQ_STAT_FWD_ARP_REQUEST || (key >= q->mode->stat_lo && key <= q->mode->stat_hi))
+        return (int64_t)q->n_stat[key];
+    return -EINVAL;
 }
 
 // The oldest batch's completion flag (the load poll makes), spun on: no HIP
