@@ -37,8 +37,9 @@
 #include "../../include/cndp_mqfwd.h"
 #include "fwd_internal.h"           // the ip4_forward queue mode's group rule and its table's reader protocol
 #include "../../include/cndp_mqcnet.h"
-#include "pcb_internal.h"           // the udp_input queue mode's per-frame rule and its table's reader protocol
+#include "pcb_internal.h"           // the udp_input and tcp_input queue modes' per-frame rules and their tables' reader protocols
 #include "../../include/cndp_mql4.h"
+#include "../../include/cndp_mqtcp.h"
 
 #define CNDP_VERSION "cndp_amd 0.1 (gfx950)"
 
@@ -8003,6 +8004,166 @@ static int mq_udp_lds_init(void)
     return ok;
 }
 
+// cnet's tcp_input node and cnet_tcp_input's opening (cndp_mqtcp.h,
+// tcp_input.c:41-119, cnet_tcp.c:3386-3414).  A block is one wave; a lane owns
+// one mbuf for the demux: the IPv4 and TCP header windows, the key, the
+// BEST_MATCH lookup in the table's TCP index where it lies in device memory
+// (pcb_tcp_lookup, pcb_internal.h: an exact 4-tuple hash -- a probe or two --
+// then the port's wildcard run; the image is at most 120 KiB, read by every wave
+// of every batch, so it stays in L2), the decision and the segment record
+// (pcb_tcp_rule: the text cndp_tcp_input_node_host runs).  Every hit is
+// verified: a ballot lists the lanes that hit, a wave-uniform loop takes up to
+// four of them a turn, and each 16-lane group sums one segment -- the owner's
+// addresses, length and pseudo-header sum travel by shuffle, the loads are
+// 16-byte aligned ones with head and tail masked, the per-lane byte sums are
+// reduced across the group, and the verdict returns to the owner by shuffle.
+// All 64 lanes run every turn, the lanes that missed among them, so no
+// cross-lane operation is divergent.  No LDS, no second launch, no atomic but
+// mq_complete's ticket.
+//   a.off[i], a.priv[i]  as k_mq_udp_input has them (mq_fill_udp prepares both)
+// Bytes past the readable ones read as zero; a 16-byte load that would leave
+// [mtod - front, mtod + readable + back) is made byte by byte inside the
+// segment instead.  Nothing is written but the edge and one 32-byte record per
+// mbuf into pinned memory: {PCB index | total_length << 16, ports, faddr, laddr}
+// and the four words of struct cndp_tcp_seg, whose offset field is the header
+// length whatever it is; poll makes the node's edits and the tests that need the
+// mbuf's lengths from it (mq_wb_tcp).
+#define MQ_TCP_NOIDX 0xFFFFu
+
+__global__ __launch_bounds__(MQ_TPB) void k_mq_tcp_input(MqArgs a, const uint32_t *__restrict__ img)
+{
+    const uint32_t lane = threadIdx.x, gl = lane & 15u, grp = lane >> 4;
+    const uint32_t flags = img[2];
+    const uint32_t seg_edge = CNDP_MQ_EDGE(CNDP_MQ_NODE_TCP_INPUT, CNDP_TCP_INPUT_SEGMENT);
+    for (uint32_t base = blockIdx.x * MQ_TPB; base < a.n; base += gridDim.x * MQ_TPB) {
+        const uint32_t i = base + lane;
+        const bool live = i < a.n;
+        const uint8_t *p = nullptr;
+        uint32_t R = 0, l3 = 0, front = 0, back = 0;
+        if (live) {
+            const uint64_t pv = a.priv[i], o = a.off[i];
+            l3 = (uint32_t)pv & 0x1ffu;
+            R = (uint32_t)(pv >> MQ_UDP_R_SHIFT) & 0xffffu;
+            front = (uint32_t)(pv >> MQ_UDP_FRONT_SHIFT) & 15u;
+            back = (uint32_t)(pv >> MQ_UDP_BACK_SHIFT) & 15u;
+            if (!a.zc)
+                p = o <= a.slab_len && R <= a.slab_len - o ? a.slab + o : nullptr; // never from mq_fill_udp
+            else
+                p = (const uint8_t *)(uintptr_t)o;
+        }
+        const bool taken = p != nullptr;
+        uint32_t edge = MQ_EDGE_NONE, idx = MQ_TCP_NOIDX, ports = 0, faddr = 0, laddr = 0, L = 0, tot = 0, proto = 0;
+        uint32_t sg[4] = {0u, 0u, 0u, 0u};
+        bool need = false;
+        if (taken) {
+            const uint32_t w0 = mqf_le32(p, R, 0);
+            uint32_t th[5];
+#pragma unroll
+            for (uint32_t k = 0; k < 5u; k++)
+                th[k] = mqf_le32(p, R, l3 + 4u * k);
+            proto = mqf_byte(p, R, 9);
+            faddr = mqf_le32(p, R, 12);
+            laddr = mqf_le32(p, R, 16);
+            ports = th[0];
+            tot = ((w0 >> 8) & 0xff00u) | (w0 >> 24);
+            const uint32_t hit = pcb_tcp_lookup(img, laddr, faddr, ports >> 16, ports & 0xffffu);
+            edge = pcb_tcp_rule(hit, flags, w0, th, l3, sg, &L);
+            if (hit != CNDP_PCB_NONE)
+                idx = hit;
+            need = edge == seg_edge;
+        }
+        // what a verify's group needs of its owner: the segment's readable part [lo, lo + dlen),
+        // how far in front of lo and behind its end a load may reach, the pseudo-header sum
+        const uint32_t d0 = l3 < R ? l3 : R, d1 = l3 + L < R ? l3 + L : R; // d0 <= d1 <= R
+        const uintptr_t lo_own = (uintptr_t)p + d0;
+        const uint32_t dlen_own = need ? d1 - d0 : 0u;
+        const uint32_t flo_own = d0 + front, fhi_own = R - d1 + back;
+        const uint32_t ph_own = pcb_udp_phdr_sum(faddr, laddr, proto, L);
+        bool bad = false;
+        unsigned long long todo = __ballot(need);
+        while (todo) { // wave-uniform: every lane runs every turn
+            int own = -1; // this 16-lane group's segment: the grp-th lowest lane still to do
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) {
+                if (todo) {
+                    if (k == grp)
+                        own = __ffsll((long long)todo) - 1;
+                    todo &= todo - 1ull;
+                }
+            }
+            const int src = own >= 0 ? own : 0;
+            const uintptr_t lo = (uintptr_t)__shfl((uint32_t)lo_own, src, 64) |
+                                 (uintptr_t)__shfl((uint32_t)((uint64_t)lo_own >> 32), src, 64) << 32;
+            const uint32_t dl = __shfl(dlen_own, src, 64);
+            const uint32_t dlen = own >= 0 ? dl : 0u; // a group without a segment this turn sums nothing
+            const uint32_t flo = __shfl(flo_own, src, 64), fhi = __shfl(fhi_own, src, 64);
+            const uint32_t ph = __shfl(ph_own, src, 64);
+            uint32_t se = 0, so = 0; // sums of the bytes at even / odd addresses
+            if (dlen) {
+                const uintptr_t hi = lo + dlen, alo = lo - flo, ahi = hi + fhi;
+                const uintptr_t A = lo & ~(uintptr_t)15;
+                const uint32_t nch = (uint32_t)((hi - A + 15u) / 16u);
+                for (uint32_t c = gl; c < nch; c += 16u) {
+                    const uintptr_t X = A + 16u * (uintptr_t)c;
+                    if (X >= alo && X + 16 <= ahi) {
+                        const u32x4 v = *(const u32x4 *)X;
+                        uint32_t d[4] = {v.x, v.y, v.z, v.w};
+                        if (X < lo || X + 16 > hi) {
+#pragma unroll
+                            for (int q = 0; q < 4; q++)
+                                d[q] = mq_udp_mask(d[q], X + 4u * q, lo, hi);
+                        }
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            se = __builtin_amdgcn_sad_u8(d[q] & 0x00ff00ffu, 0u, se);
+                            so = __builtin_amdgcn_sad_u8((d[q] >> 8) & 0x00ff00ffu, 0u, so);
+                        }
+                    } else { // a chunk that overhangs what may be touched: the segment's own bytes
+                        const uintptr_t x0 = X > lo ? X : lo, x1 = X + 16 < hi ? X + 16 : hi;
+                        for (uintptr_t x = x0; x < x1; x++) {
+                            const uint32_t bv = *(const uint8_t *)x;
+                            if (x & 1u)
+                                so += bv;
+                            else
+                                se += bv;
+                        }
+                    }
+                }
+            }
+            // words are little-endian pairs counted from the segment's first byte
+            uint32_t S = (lo & 1u) ? so + (se << 8) : se + (so << 8);
+#pragma unroll
+            for (int sh = 8; sh >= 1; sh >>= 1)
+                S += __shfl_xor(S, sh, 64);
+            const uint32_t ok = pcb_udp_cksum_ok(S, ph);
+#pragma unroll
+            for (int k = 0; k < 4; k++) { // the verdict back to its owner
+                const int ok_own = __shfl(own, k * 16, 64);
+                const uint32_t ok_v = __shfl(ok, k * 16, 64);
+                if (ok_own == (int)lane)
+                    bad = !ok_v;
+            }
+        }
+        if (bad) // verify < 0: pkt_drop, userptr left unset
+            edge = CNDP_MQ_EDGE(CNDP_MQ_NODE_TCP_INPUT, CNDP_TCP_INPUT_PKT_DROP) | CNDP_MQ_EDGE_L4_CKSUM;
+        if (live) {
+            u32x4 r, s;
+            r.x = idx | tot << 16;
+            r.y = ports;
+            r.z = faddr;
+            r.w = laddr;
+            s.x = sg[0];
+            s.y = sg[1];
+            s.z = sg[2];
+            s.w = sg[3];
+            a.rec[2u * i] = r;
+            a.rec[2u * i + 1u] = s;
+            a.edges[i] = (uint16_t)edge;
+        }
+    }
+    mq_complete(a);
+}
+
 // ip4_rewrite_node_process (ip4_rewrite.c:40-247) per packet of the node's
 // bursts: the next hop's rewrite data at mtod (:85), TTL = priv1.ttl - 1 and
 // the checksum from priv1.cksum + htons(0x0100) -- in the 4-wide loop with
@@ -8320,6 +8481,7 @@ typedef void (*mq_wb_fn)(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
 #define MQ_BY_FWD 1u   // cndp_gpu_mq_create_fwd
 #define MQ_BY_IPF 2u   // cndp_gpu_mq_create_ip4_forward
 #define MQ_BY_UDP 3u   // cndp_gpu_mq_create_udp_input
+#define MQ_BY_TCP 4u   // cndp_gpu_mq_create_tcp_input
 #define MQ_FIB4 1u
 #define MQ_FIB6 2u
 struct MqMode {
@@ -8333,8 +8495,9 @@ struct MqMode {
     uint32_t (*stage_of)(const struct cndp_mq_conf *k); // ... or, where the conf decides, this
     uint32_t wb_span;  // staged: the frame's first bytes the kernel may change (mq_wb_span copies them back)
     bool len;          // the h_len array exists
-    uint32_t rec;      // record bytes per mbuf (0, 8, 16), staged and with host writeback ...
+    uint32_t rec;      // record bytes per mbuf (0, 8, 16, 32), staged and with host writeback ...
     bool rec_zc;       // ... and zero-copy as well
+    uint32_t seg;      // where in the record a struct cndp_tcp_seg lies for cndp_gpu_mq_poll_tcp (0: the mode has none)
     bool md;           // cnet_metadata: its addresses at h_md (zero-copy), the records' at h_rmd (host writeback)
     bool bst;          // the h_bst array exists ...
     uint32_t bst_flag; // ... or exists with this flag
@@ -8387,10 +8550,11 @@ struct cndp_gpu_mq {
     int err;                       // a launch error not yet reported (returned by the next submit)
     // cndp_gpu_mq_stat's counters by CNDP_MQ_STAT_* key: batches and mbufs launched so far, and the
     // mode's own, counted by poll
-    uint64_t n_stat[CNDP_MQ_STAT_L4_NOMD + 1];
+    uint64_t n_stat[CNDP_MQ_STAT_TCP_IPOPT + 1];
     struct cndp_mq_fwd fwd;        // cndpfwd modes (cndp_gpu_mq_create_fwd): the tables and the known ports
     cndp_fwd_tbl_t *ipf;           // CNDP_MQ_IP4_FORWARD (cndp_gpu_mq_create_ip4_forward): the forwarding table
-    cndp_pcb_tbl_t *pcb;           // CNDP_MQ_UDP_INPUT (cndp_gpu_mq_create_udp_input): the PCB table
+    cndp_pcb_tbl_t *pcb;           // CNDP_MQ_UDP_INPUT (cndp_gpu_mq_create_udp_input) and CNDP_MQ_TCP_INPUT
+                                   // (cndp_gpu_mq_create_tcp_input): the PCB table
     MqSlot slot[CNDP_MQ_DEPTH_MAX];
 };
 
@@ -8467,7 +8631,8 @@ static void mq_layout(cndp_gpu_mq_t *q)
 
 // by: the create call; fwd: the tables of a cndpfwd mode, checked by cndp_gpu_mq_create_fwd; ipf: the
 // forwarding table of CNDP_MQ_IP4_FORWARD, checked by cndp_gpu_mq_create_ip4_forward; pcb: the PCB
-// table of CNDP_MQ_UDP_INPUT, checked by cndp_gpu_mq_create_udp_input; all nullptr for the node modes
+// table of CNDP_MQ_UDP_INPUT or CNDP_MQ_TCP_INPUT, checked by cndp_gpu_mq_create_udp_input / _tcp_input; all
+// nullptr for the node modes
 static int mq_create(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, uint32_t by, const struct cndp_mq_fwd *fwd,
                      cndp_fwd_tbl_t *ipf, cndp_pcb_tbl_t *pcb, cndp_gpu_mq_t **out)
 {
@@ -8622,6 +8787,22 @@ extern "C" int cndp_gpu_mq_create_udp_input(cndp_gpu_ctx_t *c, const struct cndp
     if (r)
         return r;
     return mq_create(c, conf, MQ_BY_UDP, nullptr, nullptr, tbl, out);
+}
+
+// cndp_mqtcp.h: cnet's tcp_input node over a TCP PCB table
+extern "C" int cndp_gpu_mq_create_tcp_input(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf,
+                                            cndp_pcb_tbl_t *tbl, cndp_gpu_mq_t **out)
+{
+    if (!c || !conf || !tbl || !out)
+        return -EINVAL;
+    *out = nullptr;
+    const MqMode *m = mq_mode(conf->mode, MQ_BY_TCP);
+    if (!m || (conf->flags & ~m->flags))
+        return -EINVAL;
+    const int r = pcb_tdev_check(tbl, c->dev); // one table, one device, as cndp_gpu_tcp_input has it
+    if (r)
+        return r;
+    return mq_create(c, conf, MQ_BY_TCP, nullptr, nullptr, tbl, out);
 }
 
 extern "C" void cndp_gpu_mq_free(cndp_gpu_mq_t *q)
@@ -8802,6 +8983,20 @@ static int mq_launch_udp(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
         hipLaunchKernelGGL(k_mq_udp_input<false>, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, img);
     const bool ok = hipGetLastError() == hipSuccess;
     r = pcb_dev_end(q->pcb, q->s, ok);
+    return ok ? r : -EIO;
+}
+
+static int mq_launch_tcp(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    // the TCP mirror's reader protocol (pcb_internal.h): ordered after a reader on another stream,
+    // the TCP image mirrored on this one, our end recorded for the next reader
+    const uint32_t *img = nullptr;
+    int r = pcb_tdev_begin(q->pcb, q->c->dev, q->s, &img);
+    if (r)
+        return r;
+    hipLaunchKernelGGL(k_mq_tcp_input, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, img);
+    const bool ok = hipGetLastError() == hipSuccess;
+    r = pcb_tdev_end(q->pcb, q->s, ok);
     return ok ? r : -EIO;
 }
 
@@ -9433,6 +9628,32 @@ static void mq_wb_udp(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
     }
 }
 
+// tcp_input: every edit of the node, and the steps that need the mbuf's lengths, from the device's
+// records, zero-copy or staged (pcb_tcp_apply, pcb_internal.h: the text the host twin runs); the
+// mbuf's edge, its record and the eight counters are what that answers
+static void mq_wb_tcp(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
+{
+    u32x4 *rec = (u32x4 *)(sl->h + q->h_rec);
+    uint16_t *edw = (uint16_t *)(sl->h + q->h_edge);
+    for (uint32_t i = i0; i < i1; i++) {
+        if (i + MQ_PF < i1)
+            __builtin_prefetch(sl->mb[i + MQ_PF], 1);
+        const uint32_t e = edw[i];
+        if (e == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
+            continue;
+        uint8_t *m = (uint8_t *)sl->mb[i];
+        const u32x4 r = rec[2u * i];
+        const uint32_t idx = r.x & 0xFFFFu;
+        uint64_t user = 0;
+        if (idx < q->pcb->max) // a value set while the batch was in flight may or may not show
+            user = __atomic_load_n(&q->pcb->user[idx], __ATOMIC_RELAXED);
+        const uint32_t out = pcb_tcp_apply(m, mq_md_host(q, m), e, user, r.y, r.z, r.w, r.x >> 16,
+                                           (struct cndp_tcp_seg *)&rec[2u * i + 1u]);
+        edw[i] = (uint16_t)out;
+        q->n_stat[out >> 16]++;
+    }
+}
+
 // ip4_forward: pktmbuf_adjust(m, -l2_len) on the host, zero-copy or staged; staged also the frame
 // bytes, in the reference's order: TTL / checksum at the old mtod, then the MAC bytes at
 // the new one (which win where l2_len < 12 makes them overlap), each below buf_len
@@ -9668,6 +9889,12 @@ static const MqMode mq_modes[] = {
      .stage_of = mq_stage_udp, .len = true, .rec = 16, .rec_zc = true,
      .stat_lo = CNDP_MQ_STAT_L4_RECV, .stat_hi = CNDP_MQ_STAT_L4_NOMD,
      .fill = mq_fill_udp, .launch = mq_launch_udp, .wb_zc = mq_wb_udp, .wb_staged = mq_wb_udp},
+    // the frame words are the UDP mode's (mq_fill_udp); its counters are kept by its writeback,
+    // where the outcomes that need the mbuf's lengths are decided
+    {.mode = CNDP_MQ_TCP_INPUT, .by = MQ_BY_TCP,
+     .stage_of = mq_stage_udp, .len = true, .rec = 32, .rec_zc = true, .seg = 16,
+     .stat_lo = CNDP_MQ_STAT_TCP_SEGMENT, .stat_hi = CNDP_MQ_STAT_TCP_IPOPT,
+     .fill = mq_fill_udp, .launch = mq_launch_tcp, .wb_zc = mq_wb_tcp, .wb_staged = mq_wb_tcp},
 };
 
 static const MqMode *mq_mode(uint32_t mode, uint32_t by)
@@ -9676,7 +9903,8 @@ static const MqMode *mq_mode(uint32_t mode, uint32_t by)
     return mode < n && mq_modes[mode].mode == mode && mq_modes[mode].by == by ? &mq_modes[mode] : nullptr;
 }
 
-extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, uint32_t max)
+// segs: cndp_gpu_mq_poll_tcp's records (nullptr: none wanted)
+static int mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, struct cndp_tcp_seg *segs, uint32_t max)
 {
     if (!q || (max && (!mbufs || !edges)))
         return -EINVAL;
@@ -9724,6 +9952,16 @@ extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges,
             q->writeback(q, sl, sl->polled, sl->polled + take);
         memcpy(mbufs + got, sl->mb + sl->polled, (size_t)take * sizeof(void *));
         memcpy(edges + got, (const uint16_t *)(sl->h + q->h_edge) + sl->polled, (size_t)take * 2);
+        if (segs) // the records of the mbufs that leave on SEGMENT, zero for the rest (a failed slot's too)
+            for (uint32_t i = 0; i < take; i++) {
+                const bool on = (edges[got + i] & CNDP_MQ_EDGE_TCP_MASK) ==
+                                CNDP_MQ_EDGE(CNDP_MQ_NODE_TCP_INPUT, CNDP_TCP_INPUT_SEGMENT);
+                if (on)
+                    memcpy(&segs[got + i], sl->h + q->h_rec + (uint64_t)(sl->polled + i) * q->mode->rec + q->mode->seg,
+                           sizeof(*segs));
+                else
+                    memset(&segs[got + i], 0, sizeof(*segs));
+            }
         if (q->mode->count) // the mode's counters, from the edges handed back
             q->mode->count(q, edges + got, take);
         sl->polled += take;
@@ -9737,15 +9975,29 @@ extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges,
     return (int)got;
 }
 
+extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, uint32_t max)
+{
+    return mq_poll(q, mbufs, edges, nullptr, max);
+}
+
+// cndp_mqtcp.h: poll, and each returned mbuf's struct cndp_tcp_seg
+extern "C" int cndp_gpu_mq_poll_tcp(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, struct cndp_tcp_seg *segs,
+                                    uint32_t max)
+{
+    if (!q || !q->mode->seg)
+        return -EINVAL;
+    return mq_poll(q, mbufs, edges, segs, max);
+}
+
 // Batches, mbufs and the cndpfwd and ip4_forward families answer on every mode (0 where the mode
 // does not count them).  The keys of a family added later are known only to the mode that counts
 // them: on every other mode they stay the unknown keys they were before that mode existed.
 static_assert(CNDP_MQ_STAT_BATCHES == 1 && CNDP_MQ_STAT_FWD_ARP_REQUEST == 10 && CNDP_MQ_STAT_L4_RECV == 11 &&
-                  CNDP_MQ_STAT_L4_NOMD == 16,
+                  CNDP_MQ_STAT_L4_NOMD == 16 && CNDP_MQ_STAT_TCP_SEGMENT == 17 && CNDP_MQ_STAT_TCP_IPOPT == 24,
               "cndp_gpu_mq_stat's key ranges");
 extern "C" int64_t cndp_gpu_mq_stat(const cndp_gpu_mq_t *q, int key)
 {
-    if (!q || key < CNDP_MQ_STAT_BATCHES || key > CNDP_MQ_STAT_L4_NOMD)
+    if (!q || key < CNDP_MQ_STAT_BATCHES || key > CNDP_MQ_STAT_TCP_IPOPT)
         return -EINVAL;
     if (key <= CNDP_MQ_STAT_FWD_ARP_REQUEST || (key >= q->mode->stat_lo && key <= q->mode->stat_hi))
         return (int64_t)q->n_stat[key];

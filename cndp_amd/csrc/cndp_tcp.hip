@@ -20,6 +20,11 @@
 //                     fails gets the drop values written over its outputs.
 // Every frame read is bounded by slab_len; no load leaves the slab.
 //
+// The TCP image's device mirror is one buffer guarded by an event.  Every reader
+// -- cndp_gpu_tcp_input here, the mbuf queue's CNDP_MQ_TCP_INPUT kernel in
+// cndp_gpu.hip -- brackets its launch with pcb_tdev_begin / pcb_tdev_end
+// (pcb_internal.h).
+//
 // The byte readers and the checksum arithmetic are those of cndp_l4.hip, kept as
 // a copy so that translation unit stays as it is.
 #include <hip/hip_runtime.h>
@@ -437,11 +442,16 @@ static int tcp_dev_get(struct cndp_pcb_tbl *t, int dev, TcpDev **out)
     return 0;
 }
 
-static int tcp_run(TcpDev *d, struct cndp_pcb_tbl *t, const struct cndp_batch *b,
-                   const struct cndp_tcp_io *io, hipStream_t s)
+// pcb_tdev_begin under t->lock: the device, the host image, the wait for a
+// reader on another stream, the mirror brought up to date
+static int tcp_begin_locked(struct cndp_pcb_tbl *t, int dev, hipStream_t s, TcpDev **out)
 {
-    int r = pcb_tcp_image(t);
+    HIP_TRY(hipSetDevice(dev));
+    TcpDev *d = NULL;
+    int r = tcp_dev_get(t, dev, &d);
     if (r)
+        return r;
+    if ((r = pcb_tcp_image(t)))
         return r;
     if (d->have_last && d->last != s)
         HIP_TRY(hipStreamWaitEvent(s, d->ev, 0));
@@ -458,8 +468,54 @@ static int tcp_run(TcpDev *d, struct cndp_pcb_tbl *t, const struct cndp_batch *b
         HIP_TRY(hipStreamSynchronize(s)); // the host table may change after we return
         d->gen = t->timg_gen;
     }
-    if (b->n == 0)
+    *out = d;
+    return 0;
+}
+
+// pcb_tdev_end under t->lock: the reader's end recorded
+static int tcp_end_locked(struct cndp_pcb_tbl *t, hipStream_t s, int launched)
+{
+    TcpDev *d = (TcpDev *)t->tdev;
+    if (!launched || !d)
         return 0;
+    HIP_TRY(hipEventRecord(d->ev, s));
+    d->last = s;
+    d->have_last = 1;
+    return 0;
+}
+
+extern "C" int pcb_tdev_begin(struct cndp_pcb_tbl *t, int dev, void *stream, const uint32_t **img)
+{
+    pthread_mutex_lock(&t->lock);
+    TcpDev *d = NULL;
+    const int r = tcp_begin_locked(t, dev, (hipStream_t)stream, &d);
+    if (r) {
+        pthread_mutex_unlock(&t->lock);
+        return r;
+    }
+    *img = d->img;
+    return 0;
+}
+
+extern "C" int pcb_tdev_end(struct cndp_pcb_tbl *t, void *stream, int launched)
+{
+    const int r = tcp_end_locked(t, (hipStream_t)stream, launched);
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+extern "C" int pcb_tdev_check(struct cndp_pcb_tbl *t, int dev)
+{
+    pthread_mutex_lock(&t->lock);
+    const TcpDev *d = (const TcpDev *)t->tdev;
+    const int r = d && d->dev != dev ? -EINVAL : 0; // one table, one device
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+static int tcp_run(TcpDev *d, struct cndp_pcb_tbl *t, const struct cndp_batch *b,
+                   const struct cndp_tcp_io *io, hipStream_t s)
+{
     const uint32_t lds = t->timg_words * 4u;
     if (lds > TCP_LDS_MAX)
         return -E2BIG; // cannot happen within CNDP_PCB_MAX_ENTRIES (pcb_internal.h)
@@ -504,9 +560,6 @@ static int tcp_run(TcpDev *d, struct cndp_pcb_tbl *t, const struct cndp_batch *b
     // the same grid, reading each segment's count on the device
     hipLaunchKernelGGL(tcp_cksum_kernel, dim3(grid), dim3(TCP_BLOCK), 0, s, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev, s));
-    d->last = s;
-    d->have_last = 1;
     return 0;
 }
 
@@ -525,9 +578,13 @@ extern "C" int cndp_gpu_tcp_input(cndp_gpu_ctx_t *ctx, cndp_pcb_tbl_t *tbl, cons
         r = -EINVAL;
     TcpDev *d = NULL;
     if (!r)
-        r = tcp_dev_get(tbl, dev, &d);
-    if (!r)
-        r = tcp_run(d, tbl, b, io, (hipStream_t)stream);
+        r = tcp_begin_locked(tbl, dev, (hipStream_t)stream, &d);
+    if (!r) {
+        if (b->n)
+            r = tcp_run(d, tbl, b, io, (hipStream_t)stream);
+        const int e = tcp_end_locked(tbl, (hipStream_t)stream, b->n && !r);
+        r = r ? r : e;
+    }
     pthread_mutex_unlock(&tbl->lock);
     return r;
 }

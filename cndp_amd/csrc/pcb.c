@@ -433,3 +433,95 @@ int cndp_udp_input_node_host(cndp_pcb_tbl_t *t, void *const *mbufs, uint32_t n, 
     pthread_mutex_unlock(&t->lock);
     return 0;
 }
+
+/* ---- cndp_mqtcp.h: the tcp_input node over mbufs on the host ---------------- */
+
+/* the segment's little-endian 16-bit words summed, a last odd byte as a low byte
+ * (cne_raw_cksum's sum before its reduce); below 2^31 for every length */
+static inline uint32_t tcp_raw_sum(const uint8_t *p, uint32_t len)
+{
+    uint32_t S = 0, k = 0;
+    for (; k + 2u <= len; k += 2u) {
+        uint16_t w;
+        memcpy(&w, p + k, 2);
+        S += w;
+    }
+    if (k < len)
+        S += p[k];
+    return S;
+}
+
+int cndp_tcp_input_node_host(cndp_pcb_tbl_t *t, void *const *mbufs, uint32_t n, uint16_t *edges,
+                             struct cndp_tcp_seg *segs, const void *readable_end, uint32_t stage_max,
+                             void *(*metadata)(const void *m))
+{
+    if (!t || n > 256u || (n && (!mbufs || !edges)))
+        return -EINVAL;
+    pthread_mutex_lock(&t->lock);
+    int r = pcb_tcp_image(t);
+    if (r) {
+        pthread_mutex_unlock(&t->lock);
+        return r;
+    }
+    const uint32_t *img = t->timg;
+    const uint32_t flags = img[2];
+    const uintptr_t end = (uintptr_t)readable_end;
+    for (uint32_t i = 0; i < n; i++) {
+        uint8_t *m = (uint8_t *)mbufs[i];
+        edges[i] = (uint16_t)CNDP_MQ_EDGE_NONE;
+        if (segs)
+            memset(&segs[i], 0, sizeof(segs[i]));
+        if (!m || (end && (uintptr_t)m + 64u > end))
+            continue;
+        uint64_t buf, txo;
+        uint16_t doff, blen, dlen;
+        memcpy(&buf, m + PCB_MB_BUF_ADDR, 8);
+        memcpy(&txo, m + PCB_MB_TX_OFFLOAD, 8);
+        memcpy(&doff, m + PCB_MB_DATA_OFF, 2);
+        memcpy(&blen, m + PCB_MB_BUF_LEN, 2);
+        memcpy(&dlen, m + PCB_MB_DATA_LEN, 2);
+        const uintptr_t fa = (uintptr_t)buf + doff;
+        if (end && fa >= end)
+            continue; /* the frame lies outside the region */
+        const uint8_t *f = (const uint8_t *)fa;
+        /* the readable bytes: data_len, clipped at the buffer's end, the region's and stage_max */
+        uint32_t R = dlen;
+        const uint32_t room = blen > doff ? (uint32_t)(blen - doff) : 0u;
+        R = R < room ? R : room;
+        if (end && end - fa < R)
+            R = (uint32_t)(end - fa);
+        if (stage_max && stage_max < R)
+            R = stage_max;
+        const uint32_t l3 = (uint32_t)((txo >> 7) & 0x1ffu);
+        uint8_t *md = metadata ? (uint8_t *)metadata(m) : m + 64;
+        struct cndp_tcp_seg seg;
+        memset(&seg, 0, sizeof(seg));
+        uint32_t e = 0, hit = CNDP_PCB_NONE, ports = 0, faddr = 0, laddr = 0, tot = 0;
+        if (md) {
+            uint32_t th[5], sw[4], L;
+            for (uint32_t k = 0; k < 5u; k++)
+                th[k] = fr32(f, R, l3 + 4u * k);
+            const uint32_t w0 = fr32(f, R, 0);
+            faddr = fr32(f, R, 12);
+            laddr = fr32(f, R, 16);
+            ports = th[0];
+            tot = ((w0 >> 8) & 0xff00u) | (w0 >> 24);
+            hit = pcb_tcp_lookup(img, laddr, faddr, ports >> 16, ports & 0xffffu);
+            e = pcb_tcp_rule(hit, flags, w0, th, l3, sw, &L);
+            memcpy(&seg, sw, sizeof(seg));
+            if (e == PCB_TCP_E(CNDP_TCP_INPUT_SEGMENT)) {
+                const uint32_t d0 = l3 < R ? l3 : R, d1 = l3 + L < R ? l3 + L : R;
+                const uint32_t S = tcp_raw_sum(f + d0, d1 - d0);
+                if (!pcb_udp_cksum_ok(S, pcb_udp_phdr_sum(faddr, laddr, fr8(f, R, 9), L)))
+                    e = PCB_TCP_E(CNDP_TCP_INPUT_PKT_DROP) | CNDP_MQ_EDGE_L4_CKSUM;
+            }
+        }
+        const uint32_t out = pcb_tcp_apply(m, md, e, hit == CNDP_PCB_NONE ? 0u : t->user[hit], ports, faddr, laddr,
+                                           tot, &seg);
+        edges[i] = (uint16_t)out;
+        if (segs)
+            segs[i] = seg;
+    }
+    pthread_mutex_unlock(&t->lock);
+    return 0;
+}

@@ -10,6 +10,7 @@
 
 #include "../../include/cndp_tcp.h" /* includes cndp_l4.h */
 #include "../../include/cndp_mql4.h"
+#include "../../include/cndp_mqtcp.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -343,6 +344,124 @@ static inline PCB_HD uint32_t pcb_tcp_lookup(const uint32_t *img, uint32_t laddr
 
 /* Call with tbl->lock held: bring tbl->timg up to date.  0 or -ENOMEM. */
 int pcb_tcp_image(struct cndp_pcb_tbl *tbl);
+
+/* Readers of the TCP image's device mirror (cndp_tcp.hip): cndp_gpu_tcp_input
+ * and the mbuf queue's CNDP_MQ_TCP_INPUT kernel in cndp_gpu.hip.  The protocol
+ * is pcb_dev_begin / _end / _check's, over tbl->tdev and the TCP image. */
+int pcb_tdev_begin(struct cndp_pcb_tbl *tbl, int dev, void *stream, const uint32_t **img);
+int pcb_tdev_end(struct cndp_pcb_tbl *tbl, void *stream, int launched);
+int pcb_tdev_check(struct cndp_pcb_tbl *tbl, int dev);
+
+/* ---- tcp_input per frame (cndp_mqtcp.h): the text the queue's kernel
+ * k_mq_tcp_input and the host twin cndp_tcp_input_node_host both compile */
+
+#define PCB_TCP_E(e) CNDP_MQ_EDGE(CNDP_MQ_NODE_TCP_INPUT, e)
+
+/* tcp_input's decision for one frame once its key is looked up (tcp_input.c:95-108)
+ * and the record of cnet_tcp_input's opening (cnet_tcp.c:3386-3414), from the words
+ * as loaded: hit = pcb_tcp_lookup's answer, flags the image's, w0 the IPv4
+ * header's first word, th[1..4] TCP header words 1-4.  Returns the edge that
+ * stands unless the sum fails: no match (final), total_length < IHL * 4, where
+ * __ipv4_udptcp_cksum sums to 0, which fails (final), else SEGMENT with *L the
+ * bytes to sum.  seg[] is struct cndp_tcp_seg as four words, computed for every
+ * frame: its offset field is the header length whatever it is, and the host side
+ * (pcb_tcp_apply) clears the record where the edge is not SEGMENT. */
+static inline PCB_HD uint32_t pcb_tcp_rule(uint32_t hit, uint32_t flags, uint32_t w0, const uint32_t *th, uint32_t l3,
+                                           uint32_t *seg, uint32_t *L)
+{
+    const uint32_t ihl = (w0 & 0xfu) * 4u, tot = ((w0 >> 8) & 0xff00u) | (w0 >> 24);
+    const uint32_t offset = (th[3] & 0xf0u) >> 2, fl = (th[3] >> 8) & 0x3fu;
+    const uint32_t synfin = (fl & 1u) + ((fl >> 1) & 1u); /* tcp_syn_fin_cnt[flags & SYN_FIN] */
+    const uint32_t s = th[1], a = th[2];
+    seg[0] = (s >> 24) | ((s >> 8) & 0xff00u) | ((s << 8) & 0xff0000u) | (s << 24);
+    seg[1] = (a >> 24) | ((a >> 8) & 0xff00u) | ((a << 8) & 0xff0000u) | (a << 24);
+    seg[2] = (((th[3] >> 8) & 0xff00u) | (th[3] >> 24)) | (((th[4] >> 8) & 0xff00u) | (th[4] >> 24)) << 16;
+    seg[3] = ((tot - (offset + l3) + synfin) & 0xffffu) | fl << 16 | offset << 24;
+    *L = 0;
+    if (hit == CNDP_PCB_NONE)
+        return PCB_TCP_E((flags & PCB_F_PUNT) ? CNDP_TCP_INPUT_PKT_PUNT : CNDP_TCP_INPUT_PKT_DROP);
+    if (tot < ihl)
+        return PCB_TCP_E(CNDP_TCP_INPUT_PKT_DROP) | CNDP_MQ_EDGE_L4_CKSUM;
+    *L = tot - ihl;
+    return PCB_TCP_E(CNDP_TCP_INPUT_SEGMENT);
+}
+
+/* Steps 1 and 5-10 of cndp_mqtcp.h for one mbuf on the host: the twin makes them
+ * as it goes, cndp_gpu_mq_poll from the device's record.  edge is the frame's
+ * decision with the verify's verdict in (pcb_tcp_rule, then CNDP_MQ_EDGE_L4_CKSUM
+ * where the sum failed); md is metadata(m) or NULL; user the matched PCB's user
+ * value; tot the header's total_length; *seg pcb_tcp_rule's record, cleared here
+ * unless the mbuf leaves on SEGMENT.  Returns the mbuf's edge | its
+ * CNDP_MQ_STAT_TCP_* key << 16. */
+static inline uint32_t pcb_tcp_apply(uint8_t *m, uint8_t *md, uint32_t edge, uint64_t user, uint32_t ports,
+                                     uint32_t faddr, uint32_t laddr, uint32_t tot, struct cndp_tcp_seg *seg)
+{
+    const uint32_t drop = PCB_TCP_E(CNDP_TCP_INPUT_PKT_DROP);
+    const uint32_t offset = seg->offset;
+    uint32_t out;
+    if (!md) { /* tcp_input.c:55-57 */
+        out = drop | CNDP_MQ_STAT_TCP_NOMD << 16;
+        goto clear;
+    }
+    {
+        const uint16_t fport = (uint16_t)ports, lport = (uint16_t)(ports >> 16);
+        memcpy(md + 2, &fport, 2); /* :91-92, before the lookup */
+        memcpy(md + PCB_MD_LADDR + 2, &lport, 2);
+    }
+    if (edge != PCB_TCP_E(CNDP_TCP_INPUT_SEGMENT)) { /* no PCB, or verify < 0: userptr and the header stay */
+        out = edge | (uint32_t)((edge & CNDP_MQ_EDGE_L4_CKSUM) ? CNDP_MQ_STAT_TCP_CKSUM : CNDP_MQ_STAT_TCP_NOMATCH) << 16;
+        goto clear;
+    }
+    memcpy(m + PCB_MB_USERPTR, &user, 8);
+    md[0] = md[PCB_MD_LADDR] = PCB_AF_INET; /* in_caddr_copy of the key: the rest of the union is zero */
+    md[1] = md[PCB_MD_LADDR + 1] = 4;
+    memcpy(md + 4, &faddr, 4);
+    memset(md + 8, 0, 12);
+    memcpy(md + PCB_MD_LADDR + 4, &laddr, 4);
+    memset(md + PCB_MD_LADDR + 8, 0, 12);
+    {
+        uint64_t txo;
+        uint16_t doff, blen, dlen;
+        memcpy(&txo, m + PCB_MB_TX_OFFLOAD, 8);
+        memcpy(&doff, m + PCB_MB_DATA_OFF, 2);
+        memcpy(&blen, m + PCB_MB_BUF_LEN, 2);
+        memcpy(&dlen, m + PCB_MB_DATA_LEN, 2);
+        const uint32_t l3 = (uint32_t)((txo >> 7) & 0x1ffu);
+        const int badoff = offset < 20u || offset > tot;
+        if (l3 != 20u) { /* IPv4 options: the mbuf stays as cnet_tcp_input is handed it */
+            if (badoff)
+                memset(seg, 0, sizeof(*seg)); /* what cndp_gpu_tcp_input records for it */
+            return edge | CNDP_MQ_EDGE_TCP_IPOPT | CNDP_MQ_STAT_TCP_IPOPT << 16;
+        }
+        /* pktmbuf_adjust(m, l3_len), pktmbuf.h:955-971 */
+        if (l3 > dlen || l3 + doff > blen) {
+            out = drop | CNDP_MQ_STAT_TCP_ADJUST << 16;
+            goto clear;
+        }
+        doff = (uint16_t)(doff + l3);
+        dlen = (uint16_t)(dlen - l3);
+        memcpy(m + PCB_MB_DATA_OFF, &doff, 2);
+        memcpy(m + PCB_MB_DATA_LEN, &dlen, 2);
+        if (dlen < 20u) { /* rx_short: the adjust stays */
+            out = drop | CNDP_MQ_STAT_TCP_SHORT << 16;
+            goto clear;
+        }
+        if (offset <= dlen && offset + doff <= blen) { /* pktmbuf_adj_offset(m, offset): silent when it does not fit */
+            doff = (uint16_t)(doff + offset);
+            dlen = (uint16_t)(dlen - offset);
+            memcpy(m + PCB_MB_DATA_OFF, &doff, 2);
+            memcpy(m + PCB_MB_DATA_LEN, &dlen, 2);
+        }
+        if (badoff) { /* rx_badoff, after the adj_offset */
+            out = drop | CNDP_MQ_STAT_TCP_BADOFF << 16;
+            goto clear;
+        }
+    }
+    return edge | CNDP_MQ_STAT_TCP_SEGMENT << 16;
+clear:
+    memset(seg, 0, sizeof(*seg));
+    return out;
+}
 
 #ifdef __cplusplus
 }

@@ -166,6 +166,23 @@ def udp_input_node_host(tbl: PcbTable, ptrs, n: int | None = None, readable_end=
     return edges[:n]
 
 
+def tcp_input_node_host(tbl: PcbTable, ptrs, n: int | None = None, readable_end=None, stage_max: int = 0,
+                        metadata=None):
+    """cndp_tcp_input_node_host (include/cndp_mqtcp.h): tcp_input and the
+    opening of cnet_tcp_input on the calling thread over one burst of n <= 256
+    mbufs, the mbufs' userptr / data_off / data_len and their metadata edited
+    in place.  Arguments as udp_input_node_host.  Returns (edges, segs), segs
+    a SEG_DT record array."""
+    n = len(ptrs) if n is None else n
+    edges = np.zeros(max(n, 1), np.uint16)
+    segs = np.zeros(max(n, 1), SEG_DT)
+    fn = METADATA_FN(metadata) if metadata else None
+    N.check(N.lib().cndp_tcp_input_node_host(tbl.h, ptrs, n, edges.ctypes.data, segs.ctypes.data, readable_end,
+                                             stage_max, ctypes.cast(fn, ctypes.c_void_p) if fn else None),
+            "cndp_tcp_input_node_host")
+    return edges[:n], segs[:n]
+
+
 def alloc_l4_outputs(n: int, device) -> dict:
     """The output arrays of cndp_gpu_udp_input as torch tensors (signed
     dtypes of the same width, as Classifier.alloc_outputs uses)."""

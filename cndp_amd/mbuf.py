@@ -15,6 +15,7 @@ import ctypes
 import numpy as np
 
 from . import native as N
+from .l4 import SEG_DT
 
 # struct pktmbuf_s, 64 bytes (pktmbuf.h:102-204)
 MBUF_DT = np.dtype([("pooldata", "<u8"), ("buf_addr", "<u8"), ("hash", "<u4"), ("meta_index", "<u4"),
@@ -124,7 +125,9 @@ class MbufQueue:
         resolves in; it must outlive the queue.
         CNDP_MQ_UDP_INPUT (cndp_mql4.h): pcb_tbl is the PcbTable ip4_proto +
         udp_input demultiplex in; it must outlive the queue.  metadata is the
-        hook poll calls (returning 0 / None stands for NULL)."""
+        hook poll calls (returning 0 / None stands for NULL).
+        CNDP_MQ_TCP_INPUT (cndp_mqtcp.h): pcb_tbl is the TCP PcbTable tcp_input
+        looks connections up in; the create call is chosen by the mode."""
         self._L = N.lib()
         self._keep = (fib, acl, fwd_tbl, pcb_tbl)
         c = N.MqConf()
@@ -149,6 +152,9 @@ class MbufQueue:
         elif fwd_tbl is not None:
             N.check(self._L.cndp_gpu_mq_create_ip4_forward(cl.h, ctypes.byref(c), fwd_tbl.h, ctypes.byref(h)),
                     "cndp_gpu_mq_create_ip4_forward")
+        elif pcb_tbl is not None and mode == N.CNDP_MQ_TCP_INPUT:
+            N.check(self._L.cndp_gpu_mq_create_tcp_input(cl.h, ctypes.byref(c), pcb_tbl.h, ctypes.byref(h)),
+                    "cndp_gpu_mq_create_tcp_input")
         elif pcb_tbl is not None:
             N.check(self._L.cndp_gpu_mq_create_udp_input(cl.h, ctypes.byref(c), pcb_tbl.h, ctypes.byref(h)),
                     "cndp_gpu_mq_create_udp_input")
@@ -192,12 +198,35 @@ class MbufQueue:
         k = N.check(self._L.cndp_gpu_mq_poll(self.h, out, edges.ctypes.data, max_n), "cndp_gpu_mq_poll")
         return np.array([x or 0 for x in out[:k]], dtype=np.uint64), edges[:k].copy()
 
-    def run(self, pool: MbufPool, idx, bursts):
+    def poll_tcp(self, max_n: int = 1 << 16):
+        """cndp_gpu_mq_poll_tcp (include/cndp_mqtcp.h): poll, and each returned
+        mbuf's struct cndp_tcp_seg as a record array (l4.SEG_DT)."""
+        out = (ctypes.c_void_p * max_n)()
+        edges = np.zeros(max_n, np.uint16)
+        segs = np.zeros(max_n, SEG_DT)
+        k = N.check(self._L.cndp_gpu_mq_poll_tcp(self.h, out, edges.ctypes.data, segs.ctypes.data, max_n),
+                    "cndp_gpu_mq_poll_tcp")
+        return np.array([x or 0 for x in out[:k]], dtype=np.uint64), edges[:k].copy(), segs[:k].copy()
+
+    def run_tcp(self, pool: MbufPool, idx, bursts):
+        """run() with poll_tcp: (addresses, edges, segs) in completion order."""
+        segs = []
+
+        def poll():
+            a, e, s = self.poll_tcp()
+            segs.append(s)
+            return a, e
+        a, e = self.run(pool, idx, bursts, poll=poll)
+        return a, e, np.concatenate(segs) if segs else np.zeros(0, SEG_DT)
+
+    def run(self, pool: MbufPool, idx, bursts, poll=None):
         """Submit mbufs pool[idx] as graph bursts of the given sizes, polling
         as a node would (drain while the queue is full), until every mbuf has
-        come back.  Returns (addresses, edges) in completion order."""
+        come back.  Returns (addresses, edges) in completion order.  poll: the
+        poll to use instead of self.poll (run_tcp's)."""
         idx = np.asarray(idx, dtype=np.int64)
         got_a, got_e = [], []
+        poll = poll or self.poll
         pos = 0
         for b in bursts:
             ptrs = pool.ptrs(idx[pos:pos + b])
@@ -205,7 +234,7 @@ class MbufQueue:
             while done < b:
                 k = self.submit(ctypes.addressof(ptrs) + done * ctypes.sizeof(ctypes.c_void_p), b - done)
                 done += k
-                a, e = self.poll()
+                a, e = poll()
                 got_a.append(a)
                 got_e.append(e)
                 if k == 0 and a.size == 0:
@@ -216,7 +245,7 @@ class MbufQueue:
                 break
             self.flush()
             self.wait()
-            a, e = self.poll()
+            a, e = poll()
             got_a.append(a)
             got_e.append(e)
         return np.concatenate(got_a) if got_a else np.zeros(0, np.uint64), \

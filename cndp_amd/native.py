@@ -2,7 +2,7 @@
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
 include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h,
 include/cndp_acl.h, include/cndp_cfwd.h, include/cndp_mqfwd.h,
-include/cndp_mqcnet.h and include/cndp_mql4.h).
+include/cndp_mqcnet.h, include/cndp_mql4.h and include/cndp_mqtcp.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -162,6 +162,13 @@ CNDP_MQ_EDGE_L4_CKSUM = 0x0080
 CNDP_MQ_EDGE_L4_MASK = 0xFF7F
 (CNDP_MQ_STAT_L4_RECV, CNDP_MQ_STAT_L4_NOMATCH, CNDP_MQ_STAT_L4_CKSUM, CNDP_MQ_STAT_L4_PROTO_DROP,
  CNDP_MQ_STAT_L4_TCP, CNDP_MQ_STAT_L4_NOMD) = range(11, 17)
+# cndp_mqtcp.h
+CNDP_MQ_TCP_INPUT = 9
+CNDP_MQ_NODE_TCP_INPUT = 5
+CNDP_MQ_EDGE_TCP_IPOPT = 0x0040
+CNDP_MQ_EDGE_TCP_MASK = 0xFF3F
+(CNDP_MQ_STAT_TCP_SEGMENT, CNDP_MQ_STAT_TCP_NOMATCH, CNDP_MQ_STAT_TCP_CKSUM, CNDP_MQ_STAT_TCP_NOMD,
+ CNDP_MQ_STAT_TCP_ADJUST, CNDP_MQ_STAT_TCP_SHORT, CNDP_MQ_STAT_TCP_BADOFF, CNDP_MQ_STAT_TCP_IPOPT) = range(17, 25)
 
 
 def CNDP_MQ_EDGE(node: int, e: int) -> int:
@@ -460,6 +467,11 @@ def lib():
         "cndp_udp_input_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p]),
         "cndp_pcb_user_set": (c_int, [c_void_p, c_uint32, ctypes.c_uint64]),
         "cndp_pcb_user_get": (c_int, [c_void_p, c_uint32, POINTER(ctypes.c_uint64)]),
+        # cndp_mqtcp.h
+        "cndp_gpu_mq_create_tcp_input": (c_int, [c_void_p, POINTER(MqConf), c_void_p, POINTER(c_void_p)]),
+        "cndp_gpu_mq_poll_tcp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
+        "cndp_tcp_input_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32,
+                                             c_void_p]),
         # cndp_tx.h
         "cndp_pcb_tx_set": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
         "cndp_pcb_tx_get": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
@@ -500,7 +512,7 @@ def exported_symbols():
     import re
     names = []
     inc = os.path.join(os.path.dirname(HERE), "include")
-    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h", "cndp_mqcnet.h", "cndp_mql4.h"):
+    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h", "cndp_mqcnet.h", "cndp_mql4.h", "cndp_mqtcp.h"):
         with open(os.path.join(inc, h)) as f:
             txt = f.read()
         names += re.findall(r"^[A-Za-z_][\w \*]*?\b((?:cne|cndp|ip4)_\w+)\s*\(", txt, re.M)

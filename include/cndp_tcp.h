@@ -21,7 +21,9 @@
  * (pktmbuf_adjust failing and rx_short, cnet_tcp.c:3371-3384; the batch carries
  * no per-frame length), tcp_strip_ip_options (it rewrites the frame), and
  * everything from "Segment Arrives" on: TCBs, options, reassembly, timers, RST
- * generation.  Errors are negative errno values.
+ * generation.  Errors are negative errno values.  Over pktmbuf_t bursts the
+ * node is a mode of the mbuf queue (cndp_mqtcp.h), which has the mbuf and makes
+ * the data_len tests as well.
  */
 #ifndef CNDP_TCP_H
 #define CNDP_TCP_H
