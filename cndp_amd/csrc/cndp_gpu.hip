@@ -40,6 +40,7 @@
 #include "pcb_internal.h"           // the udp_input and tcp_input queue modes' per-frame rules and their tables' reader protocols
 #include "../../include/cndp_mql4.h"
 #include "../../include/cndp_mqtcp.h"
+#include "tx_internal.h"            // the ip4_output queue mode's per-mbuf rule and its tables' reader protocol
 
 #define CNDP_VERSION "cndp_amd 0.1 (gfx950)"
 
@@ -8164,6 +8165,387 @@ __global__ __launch_bounds__(MQ_TPB) void k_mq_tcp_input(MqArgs a, const uint32_
     mq_complete(a);
 }
 
+// cnet's udp_output + ip4_output nodes over mbufs (cndp_mqtx.h, udp_output.c:33-65,
+// ip4_output.c:48-126): cndp_gpu_ip4_output's rule in two launches.  Both run
+// MQ_TX_TPB-lane blocks; block b owns the mbufs [b * chunk, (b + 1) * chunk), chunk a
+// multiple of MQ_TX_TPB and at most MQ_TX_GRID_MAX blocks a batch, one mbuf per lane.
+//   k_mq_tx_resolve  the PCB's transmit word, the headroom tests and the route lookup
+//                    on the source address (tx_reach_front / tx_reach_route,
+//                    tx_internal.h: the text the twin runs): how far the mbuf gets and
+//                    on which netif, kept as a word per mbuf in device memory; the
+//                    block's sum per netif of what its mbufs add to ip_ident.
+//   k_mq_tx_write    folds the rows of the blocks in front of it onto the table's
+//                    counters itself (block 0 also writes the new counters, into the
+//                    table's other set: no block reads what another writes); per pass
+//                    the segmented exclusive sum keyed by netif that tx_write_kernel
+//                    makes -- additions only, in index order, no atomic decides a
+//                    value.  The L4 checksums stay inside the wave: a ballot lists
+//                    the lanes that need one, a wave-uniform loop takes up to four a
+//                    turn, sixteen lanes sum one datagram's bytes from mtod on with
+//                    masked aligned 16-byte loads, the sum returns to the owner by
+//                    shuffle; the UDP header the lane is about to write is summed from
+//                    registers.  Then all 42 (34) header bytes are built in registers,
+//                    shifted once to the address's alignment and stored by st_image's
+//                    rule: an aligned dword where the whole dword is ours, bytes
+//                    otherwise.  Zero-copy the bytes go in place into the registered
+//                    pool, staged into the staging in front of the payload's copy.
+//   a.off[i]   zero-copy: the device address of mtod (0: not taken); staged: the
+//              offset of the payload's copy in the staging, a multiple of 16 with at
+//              least MQ_TX_FRONT bytes in front of it
+//   a.priv[i]  PCB index (0xFFFF: not taken) | min(data_off, 63) << 16 | md NULL << 22
+//              | data_len << 23 | readable bytes from mtod << 39 | front << 55 |
+//              back << 59, front / back as k_mq_udp_input has them
+//   a.rec[i]   in: {faddr, laddr, fport | lport << 16}; out, the fourth word: edge |
+//              TXS_* << 16 | (1 + the offset from mtod of checksum bytes stored outside
+//              the header) << 20 | how many << 26
+// No mbuf header and no metadata is read or written here; poll makes the header edits
+// (tx_mbuf_apply) and, staged, copies back exactly the bytes written (mq_wb_tx).
+#define MQ_TX_TPB 256u
+#define MQ_TX_GRID_MAX 64u
+#define MQ_TX_FRONT 48u
+#define MQ_TX_NOIDX 0xFFFFull
+#define MQ_TX_H_SHIFT 16u
+#define MQ_TX_NOMD (1ull << 22)
+#define MQ_TX_DLEN_SHIFT 23u
+#define MQ_TX_R_SHIFT 39u
+#define MQ_TX_FRONT_SHIFT 55u
+#define MQ_TX_BACK_SHIFT 59u
+#define MQ_TX_REC_ST_SHIFT 16u
+#define MQ_TX_REC_CK_SHIFT 20u
+#define MQ_TX_REC_CKN_SHIFT 26u
+static_assert(MQ_TX_TPB == CNDP_FWD_NETIFS, "a thread per netif");
+
+struct MqTx {
+    uint32_t mode;  // CNDP_TX_UDP / CNDP_TX_IP4
+    uint32_t chunk; // mbufs per block
+    const uint32_t *ximg; // device mirror of the PCB table's transmit image (tx_internal.h)
+    const uint32_t *img;  // device mirror of the forwarding table's object image (fwd_internal.h)
+    struct fwd_fibv arp, rt;
+    const uint16_t *ident_in; // [256]: the table's counters before the batch
+    uint16_t *ident_out;      // [256]: and after it
+    uint32_t *rows;           // [grid][256]: a block's sums per netif
+    uint32_t *state;          // per mbuf: TXS_* << 8 | netif
+};
+
+__global__ __launch_bounds__(MQ_TX_TPB) void k_mq_tx_resolve(MqArgs a, MqTx w)
+{
+    __shared__ uint32_t s_sum[CNDP_FWD_NETIFS];
+    const uint32_t t = threadIdx.x;
+    s_sum[t] = 0;
+    __syncthreads();
+    uint32_t count = w.ximg[0];
+    count = count > CNDP_PCB_MAX_ENTRIES ? CNDP_PCB_MAX_ENTRIES : count;
+    const uint32_t rt_cap = w.img[1];
+    const uint32_t *const rto = w.img + FWD_IMG_HDR + 2u * (size_t)w.img[0];
+    const uint32_t beg = blockIdx.x * w.chunk;
+    const uint32_t end = a.n - beg < w.chunk ? a.n : beg + w.chunk; // beg < n: no empty block
+    for (uint32_t i = beg + t; i < end; i += MQ_TX_TPB) {
+        const uint64_t pv = a.priv[i];
+        const uint32_t idx = (uint32_t)(pv & MQ_TX_NOIDX), H = (uint32_t)(pv >> MQ_TX_H_SHIFT) & 63u;
+        const uint32_t dlen = (uint32_t)(pv >> MQ_TX_DLEN_SHIFT) & 0xffffu;
+        uint32_t pw = idx < count ? w.ximg[TXI_HDR + idx] : 0u;
+        if (a.zc && a.off[i] == 0u)
+            pw = 0u;
+        uint32_t st = tx_reach_front(pw, (pv & MQ_TX_NOMD) != 0u, w.mode, H), nif = 0;
+        if (st == TX_ROUTE) {
+            const uint32_t ri = fwd_fib_lookup(&w.rt, __builtin_bswap32(a.rec[i].y)) & 0xffffffu;
+            const uint32_t rw = ri < rt_cap ? rto[2u * (size_t)ri + 1u] : 0u;
+            st = tx_reach_route(rw, w.mode, H);
+            if (st == TXS_OUT) {
+                nif = rw & 0xffu;
+                atomicAdd(&s_sum[nif], tx_step(tx_total(w.mode, dlen))); // a sum: the order adds nothing
+            }
+        }
+        w.state[i] = st << 8 | nif;
+    }
+    __syncthreads();
+    w.rows[(size_t)blockIdx.x * CNDP_FWD_NETIFS + t] = s_sum[t];
+}
+
+// Bytes [s, e) of the 44-byte image W, except [hs, he), to base + index, by st_image's
+// rule (cndp_tx.hip): the image is shifted once to the alignment of its address; an
+// aligned dword that lies wholly inside the bytes to store is one dword store, any other
+// one goes byte by byte.  Only bytes to store are touched; base itself may lie in front
+// of the buffer when the image's first bytes are not stored.
+__device__ __forceinline__ void mq_tx_store(uint8_t *base, const uint32_t (&W)[11], int s, int e, int hs, int he)
+{
+    const uint32_t sh = (uint32_t)((uintptr_t)base & 3u);
+    uint32_t V[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        const uint32_t lo = k > 0 ? W[k - 1] : 0u, hi = k < 11 ? W[k] : 0u;
+        V[k] = sh ? __builtin_amdgcn_alignbyte(hi, lo, 4u - sh) : hi;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        const int i0 = 4 * k - (int)sh; // the image index of the dword's first byte
+        if (i0 + 4 <= s || i0 >= e)
+            continue;
+        const bool whole = i0 >= s && i0 + 4 <= e && (i0 + 4 <= hs || i0 >= he);
+        if (whole)
+            *(uint32_t *)(base + i0) = V[k];
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int idx = i0 + j;
+                if (idx >= s && idx < e && !(idx >= hs && idx < he))
+                    base[idx] = (uint8_t)(V[k] >> (8 * j));
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MQ_TX_TPB) void k_mq_tx_write(MqArgs a, MqTx w)
+{
+    __shared__ uint32_t s_run[CNDP_FWD_NETIFS];                        // the counters at the pass's first mbuf
+    __shared__ uint32_t s_wtot[MQ_TX_TPB / 64u][CNDP_FWD_NETIFS];      // per wave of the pass: its mbufs' sum per netif
+    __shared__ uint32_t s_mac[2u * CNDP_FWD_NETIFS];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6, gl = lane & 15u, grp = lane >> 4;
+    uint32_t count = w.ximg[0];
+    count = count > CNDP_PCB_MAX_ENTRIES ? CNDP_PCB_MAX_ENTRIES : count;
+    const uint32_t arp_cap = w.img[0], rt_cap = w.img[1];
+    const uint32_t *const arpo = w.img + FWD_IMG_HDR;
+    const uint32_t *const nifs = arpo + 2u * (size_t)arp_cap + 2u * (size_t)rt_cap;
+    for (uint32_t k = t; k < 2u * CNDP_FWD_NETIFS; k += MQ_TX_TPB)
+        s_mac[k] = nifs[k];
+    for (uint32_t k = t; k < (MQ_TX_TPB / 64u) * CNDP_FWD_NETIFS; k += MQ_TX_TPB)
+        (&s_wtot[0][0])[k] = 0;
+    {
+        // the counters at this block's first mbuf: the table's plus the rows in front of it
+        uint32_t run = w.ident_in[t];
+        for (uint32_t b = 0; b < blockIdx.x; b++)
+            run += w.rows[(size_t)b * CNDP_FWD_NETIFS + t];
+        s_run[t] = run;
+        if (blockIdx.x == 0) { // run is the table's counter here: the batch's totals go to the other set
+            for (uint32_t b = 0; b < gridDim.x; b++)
+                run += w.rows[(size_t)b * CNDP_FWD_NETIFS + t];
+            w.ident_out[t] = (uint16_t)run;
+        }
+    }
+    __syncthreads();
+    const bool udp_mode = w.mode == CNDP_TX_UDP;
+    const uint32_t img_end = TX_IMG_END(w.mode), hdr = udp_mode ? 8u : 0u;
+    const uint32_t beg = blockIdx.x * w.chunk;
+    const uint32_t end = a.n - beg < w.chunk ? a.n : beg + w.chunk;
+    for (uint32_t base_i = beg; base_i < end; base_i += MQ_TX_TPB) {
+        const uint32_t i = base_i + t;
+        const bool live = i < end;
+        uint32_t st = TXS_NONE, nif = 0;
+        uint64_t pv = 0;
+        if (live) {
+            const uint32_t sw = w.state[i];
+            st = sw >> 8;
+            nif = sw & 0xffu;
+            pv = a.priv[i];
+        }
+        const uint32_t total = tx_total(w.mode, (uint32_t)(pv >> MQ_TX_DLEN_SHIFT) & 0xffffu);
+        // ---- packet_id: the netif's counter plus every earlier mbuf's step
+        const uint32_t key = st == TXS_OUT ? nif : 0xffffffffu;
+        const uint32_t step = st == TXS_OUT ? tx_step(total) : 0u;
+        uint32_t pre = 0;
+        bool last = true; // no later lane of the wave has this netif
+#pragma unroll
+        for (int j = 0; j < 64; j++) {
+            const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)key, j);
+            const uint32_t sj = (uint32_t)__builtin_amdgcn_readlane((int)step, j);
+            if (kj == key) {
+                if ((uint32_t)j < lane)
+                    pre += sj;
+                if ((uint32_t)j > lane)
+                    last = false;
+            }
+        }
+        if (st == TXS_OUT && last)
+            s_wtot[wv][nif] = pre + step;
+        __syncthreads();
+        uint32_t id = 0;
+        if (st == TXS_OUT) {
+            id = s_run[nif] + pre;
+            for (uint32_t v = 0; v < wv; v++)
+                id += s_wtot[v][nif];
+            id &= 0xffffu;
+        }
+        __syncthreads();
+        {
+            uint32_t tot = 0;
+#pragma unroll
+            for (uint32_t v = 0; v < MQ_TX_TPB / 64u; v++) {
+                tot += s_wtot[v][t];
+                s_wtot[v][t] = 0;
+            }
+            s_run[t] += tot;
+        }
+        __syncthreads(); // the next pass writes s_wtot before its first barrier
+
+        // ---- the frame: where it lies, what the PCB and the metadata say
+        uint8_t *f = nullptr; // mtod at submit
+        uint32_t R = 0, front = 0, back = 0, pw = 0, src = 0, dst = 0, ports = 0;
+        if (st != TXS_NONE) {
+            const uint64_t o = a.off[i];
+            R = (uint32_t)(pv >> MQ_TX_R_SHIFT) & 0xffffu;
+            front = (uint32_t)(pv >> MQ_TX_FRONT_SHIFT) & 15u;
+            back = (uint32_t)(pv >> MQ_TX_BACK_SHIFT) & 15u;
+            if (a.zc)
+                f = (uint8_t *)(uintptr_t)o;
+            else if (o >= MQ_TX_FRONT && o <= a.slab_len && R <= a.slab_len - o) // always, from mq_fill_tx
+                f = (uint8_t *)a.slab + o;
+            const uint32_t idx = (uint32_t)(pv & MQ_TX_NOIDX);
+            pw = idx < count ? w.ximg[TXI_HDR + idx] : 0u; // the resolve kernel saw this index inside the image
+            const u32x4 r = a.rec[i];
+            dst = r.x;
+            src = r.y;
+            ports = r.z;
+        }
+        const uint32_t proto = pw & 0xffu;
+        uint32_t U0 = 0, U1 = 0;
+        if (udp_mode) {
+            U0 = ports >> 16 | ports << 16;              // src_port = lport, dst_port = fport
+            U1 = tx_step((total - 20u) & 0xffffu);       // dgram_len, dgram_cksum = 0
+        }
+        uint32_t edge = CNDP_TX_EDGE_PKT_DROP, proto_drop = 0, d0 = 0, d1 = 0;
+        const bool l4ck = st == TXS_OUT && f && (proto == 17u ? (pw & TXW_CKSUM) != 0 : proto == 6u);
+        if (st == TXS_OUT) {
+            proto_drop = proto != 17u && proto != 6u;
+            if (!proto_drop) {
+                edge = CNDP_TX_EDGE_ARP_REQUEST;
+                const uint32_t ai = fwd_fib_lookup(&w.arp, __builtin_bswap32(dst)) & 0xffffffu;
+                uint32_t h0 = 0;
+                if (ai < arp_cap)
+                    h0 = arpo[2u * (size_t)ai];
+                if (h0 & FWD_SET) {
+                    d0 = h0 & 0xffffu;
+                    d1 = arpo[2u * (size_t)ai + 1u];
+                    edge = nif + CNDP_TX_EDGE_OUTPUT; // the route's netif, not the ARP entry's
+                }
+            }
+        }
+        // ---- the L4 checksums, inside the wave: the bytes from mtod on that l4_len covers
+        const uint32_t l4_len = total >= 20u ? total - 20u : 0u;
+        uint32_t body = l4_len > hdr ? l4_len - hdr : 0u;
+        body = body < R ? body : R;
+        const uintptr_t lo_own = (uintptr_t)f;
+        const uint32_t dlen_own = l4ck ? body : 0u;
+        const uint32_t flo_own = front, fhi_own = R - body + back;
+        uint32_t Sown = 0;
+        unsigned long long todo = __ballot(l4ck && body);
+        while (todo) { // wave-uniform: every lane runs every turn
+            int own = -1; // this 16-lane group's datagram: the grp-th lowest lane still to do
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) {
+                if (todo) {
+                    if (k == grp)
+                        own = __ffsll((long long)todo) - 1;
+                    todo &= todo - 1ull;
+                }
+            }
+            const int sl = own >= 0 ? own : 0;
+            const uintptr_t lo = (uintptr_t)__shfl((uint32_t)lo_own, sl, 64) |
+                                 (uintptr_t)__shfl((uint32_t)((uint64_t)lo_own >> 32), sl, 64) << 32;
+            const uint32_t dl = __shfl(dlen_own, sl, 64);
+            const uint32_t dlen = own >= 0 ? dl : 0u; // a group without a datagram this turn sums nothing
+            const uint32_t flo = __shfl(flo_own, sl, 64), fhi = __shfl(fhi_own, sl, 64);
+            uint32_t se = 0, so = 0; // sums of the bytes at even / odd addresses
+            if (dlen) {
+                const uintptr_t hi = lo + dlen, alo = lo - flo, ahi = hi + fhi;
+                const uintptr_t A = lo & ~(uintptr_t)15;
+                const uint32_t nch = (uint32_t)((hi - A + 15u) / 16u);
+                for (uint32_t c = gl; c < nch; c += 16u) {
+                    const uintptr_t X = A + 16u * (uintptr_t)c;
+                    if (X >= alo && X + 16 <= ahi) {
+                        const u32x4 v = *(const u32x4 *)X;
+                        uint32_t d[4] = {v.x, v.y, v.z, v.w};
+                        if (X < lo || X + 16 > hi) {
+#pragma unroll
+                            for (int q = 0; q < 4; q++)
+                                d[q] = mq_udp_mask(d[q], X + 4u * q, lo, hi);
+                        }
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            se = __builtin_amdgcn_sad_u8(d[q] & 0x00ff00ffu, 0u, se);
+                            so = __builtin_amdgcn_sad_u8((d[q] >> 8) & 0x00ff00ffu, 0u, so);
+                        }
+                    } else { // a chunk that overhangs what may be touched: the datagram's own bytes
+                        const uintptr_t x0 = X > lo ? X : lo, x1 = X + 16 < hi ? X + 16 : hi;
+                        for (uintptr_t x = x0; x < x1; x++) {
+                            const uint32_t bv = *(const uint8_t *)x;
+                            if (x & 1u)
+                                so += bv;
+                            else
+                                se += bv;
+                        }
+                    }
+                }
+            }
+            // words are little-endian pairs counted from mtod, an even offset into the L4 bytes
+            uint32_t S = (lo & 1u) ? so + (se << 8) : se + (so << 8);
+#pragma unroll
+            for (int sh = 8; sh >= 1; sh >>= 1)
+                S += __shfl_xor(S, sh, 64);
+#pragma unroll
+            for (int k = 0; k < 4; k++) { // the sum back to its owner
+                const int s_own = __shfl(own, k * 16, 64);
+                const uint32_t s_v = __shfl(S, k * 16, 64);
+                if (s_own == (int)lane)
+                    Sown = s_v;
+            }
+        }
+        uint32_t ck_at = 0, ck_n = 0; // checksum bytes stored outside the header: 1 + offset from mtod, count
+        if (l4ck) {
+            const uint32_t c = tx_l4_cksum(Sown + (udp_mode ? tx_udp_hdr_sum(U0, U1, l4_len) : 0u), total, proto, src, dst);
+            const uint32_t at = proto == 17u ? 6u : 16u; // from the L4 start
+            if (at < hdr)
+                U1 |= c << 16; // dgram_cksum, stored with the header
+            else {
+                const uint32_t p0 = at - hdr;
+                ck_at = p0 + 1u;
+                ck_n = p0 + 2u <= R ? 2u : p0 < R ? 1u : 0u;
+                if (ck_n == 2u && !((uintptr_t)(f + p0) & 1u))
+                    *(uint16_t *)(f + p0) = (uint16_t)c;
+                else {
+                    if (ck_n >= 1u)
+                        f[p0] = (uint8_t)c;
+                    if (ck_n == 2u)
+                        f[p0 + 1u] = (uint8_t)(c >> 8);
+                }
+            }
+        }
+        // ---- the headers
+        int s0, e0, hs, he;
+        tx_written(w.mode, st, edge, &s0, &e0, &hs, &he);
+        if (e0 > s0 && f) {
+            const uint32_t I0 = 0x45u | ((pw >> 16) & 0xffu) << 8 | tx_step(total) << 16;
+            const uint32_t I1 = bswap16(id); // packet_id, fragment_offset = 0
+            uint32_t I2 = ((pw >> 8) & 0xffu) | proto << 8;
+            if (st == TXS_OUT) {
+                const uint32_t hsum = (I0 & 0xffffu) + (I0 >> 16) + I1 + I2 + (src & 0xffffu) + (src >> 16) +
+                                      (dst & 0xffffu) + (dst >> 16);
+                I2 |= (~tx_reduce16(hsum) & 0xffffu) << 16;
+            }
+            const uint32_t m0 = s_mac[2u * nif], m1 = s_mac[2u * nif + 1u];
+            uint32_t W[11];
+            W[0] = d0 | d1 << 16;
+            W[1] = d1 >> 16 | m0 << 16;
+            W[2] = m0 >> 16 | m1 << 16;
+            W[3] = 0x0008u | I0 << 16;
+            W[4] = I0 >> 16 | I1 << 16;
+            W[5] = I1 >> 16 | I2 << 16;
+            W[6] = I2 >> 16 | src << 16;
+            W[7] = src >> 16 | dst << 16;
+            W[8] = dst >> 16 | U0 << 16;
+            W[9] = U0 >> 16 | U1 << 16;
+            W[10] = U1 >> 16;
+            mq_tx_store(f - img_end, W, s0, e0, hs, he);
+        }
+        if (live) {
+            const uint32_t e16 = tx_mq_edge(f || st == TXS_NONE ? st : TXS_NONE, edge, proto_drop, l4ck);
+            ((uint32_t *)&a.rec[i])[3] = e16 | st << MQ_TX_REC_ST_SHIFT | ck_at << MQ_TX_REC_CK_SHIFT |
+                                         ck_n << MQ_TX_REC_CKN_SHIFT;
+            a.edges[i] = (uint16_t)e16;
+        }
+    }
+    mq_complete(a);
+}
+
 // ip4_rewrite_node_process (ip4_rewrite.c:40-247) per packet of the node's
 // bursts: the next hop's rewrite data at mtod (:85), TTL = priv1.ttl - 1 and
 // the checksum from priv1.cksum + htons(0x0100) -- in the 4-wide loop with
@@ -8482,6 +8864,7 @@ typedef void (*mq_wb_fn)(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
 #define MQ_BY_IPF 2u   // cndp_gpu_mq_create_ip4_forward
 #define MQ_BY_UDP 3u   // cndp_gpu_mq_create_udp_input
 #define MQ_BY_TCP 4u   // cndp_gpu_mq_create_tcp_input
+#define MQ_BY_TX 5u    // cndp_gpu_mq_create_ip4_output
 #define MQ_FIB4 1u
 #define MQ_FIB6 2u
 struct MqMode {
@@ -8505,6 +8888,7 @@ struct MqMode {
     bool dev_out;      // it carries the cnet classify outputs
     bool spec;         // the launch runs the context's ptype speculation: reset when a launch fails,
                        // its error taken when a batch completes
+    uint64_t (*dev_of)(const struct cndp_mq_conf *k); // optional: the bytes of device memory its kernels keep per slot
     int stat_lo, stat_hi; // the CNDP_MQ_STAT_* keys the mode counts (0, 0: none)
     // the per-burst header walk into the open slot (room checked by the caller); fill_devhdr: with
     // CNDP_MQ_F_DEVICE_HEADERS, pointers only (nullptr: the mode ignores the flag)
@@ -8550,11 +8934,13 @@ struct cndp_gpu_mq {
     int err;                       // a launch error not yet reported (returned by the next submit)
     // cndp_gpu_mq_stat's counters by CNDP_MQ_STAT_* key: batches and mbufs launched so far, and the
     // mode's own, counted by poll
-    uint64_t n_stat[CNDP_MQ_STAT_TCP_IPOPT + 1];
+    uint64_t n_stat[CNDP_MQ_STAT_TX_CKSUM + 1];
     struct cndp_mq_fwd fwd;        // cndpfwd modes (cndp_gpu_mq_create_fwd): the tables and the known ports
-    cndp_fwd_tbl_t *ipf;           // CNDP_MQ_IP4_FORWARD (cndp_gpu_mq_create_ip4_forward): the forwarding table
-    cndp_pcb_tbl_t *pcb;           // CNDP_MQ_UDP_INPUT (cndp_gpu_mq_create_udp_input) and CNDP_MQ_TCP_INPUT
-                                   // (cndp_gpu_mq_create_tcp_input): the PCB table
+    cndp_fwd_tbl_t *ipf;           // CNDP_MQ_IP4_FORWARD (cndp_gpu_mq_create_ip4_forward) and CNDP_MQ_IP4_OUTPUT
+                                   // (cndp_gpu_mq_create_ip4_output): the forwarding table
+    cndp_pcb_tbl_t *pcb;           // CNDP_MQ_UDP_INPUT (cndp_gpu_mq_create_udp_input), CNDP_MQ_TCP_INPUT
+                                   // (cndp_gpu_mq_create_tcp_input) and CNDP_MQ_IP4_OUTPUT: the PCB table
+    uint32_t tx_mode;              // CNDP_MQ_IP4_OUTPUT: CNDP_TX_UDP or CNDP_TX_IP4
     MqSlot slot[CNDP_MQ_DEPTH_MAX];
 };
 
@@ -8626,7 +9012,7 @@ static void mq_layout(cndp_gpu_mq_t *q)
     q->d_off = q->d_win + (zc ? B * 64 : 0);
     q->d_len = q->d_off + (m->dev_out && q->devhdr ? al64(B * 8) : 0);
     q->d_md = q->d_len + (m->dev_out && q->devhdr ? al64(B * 8) : 0);
-    q->d_bytes = m->dev_out ? q->d_md + (q->devhdr ? al64(B * 8) : 0) : 64;
+    q->d_bytes = m->dev_out ? q->d_md + (q->devhdr ? al64(B * 8) : 0) : m->dev_of ? m->dev_of(&k) : 64;
 }
 
 // by: the create call; fwd: the tables of a cndpfwd mode, checked by cndp_gpu_mq_create_fwd; ipf: the
@@ -8803,6 +9189,25 @@ extern "C" int cndp_gpu_mq_create_tcp_input(cndp_gpu_ctx_t *c, const struct cndp
     if (r)
         return r;
     return mq_create(c, conf, MQ_BY_TCP, nullptr, nullptr, tbl, out);
+}
+
+// cndp_mqtx.h: cnet's udp_output + ip4_output nodes over a forwarding table and a PCB table
+extern "C" int cndp_gpu_mq_create_ip4_output(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, cndp_fwd_tbl_t *ft,
+                                             cndp_pcb_tbl_t *pt, uint32_t tx_mode, cndp_gpu_mq_t **out)
+{
+    if (!c || !conf || !ft || !pt || !out)
+        return -EINVAL;
+    *out = nullptr;
+    const MqMode *m = mq_mode(conf->mode, MQ_BY_TX);
+    if (!m || (conf->flags & ~m->flags) || tx_mode > CNDP_TX_IP4)
+        return -EINVAL;
+    int r = tx_dev_check(ft, pt, c->dev); // one table, one device, as cndp_gpu_ip4_output has it
+    if (r)
+        return r;
+    r = mq_create(c, conf, MQ_BY_TX, nullptr, ft, pt, out);
+    if (!r)
+        (*out)->tx_mode = tx_mode;
+    return r;
 }
 
 extern "C" void cndp_gpu_mq_free(cndp_gpu_mq_t *q)
@@ -8997,6 +9402,38 @@ static int mq_launch_tcp(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
     hipLaunchKernelGGL(k_mq_tcp_input, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, img);
     const bool ok = hipGetLastError() == hipSuccess;
     r = pcb_tdev_end(q->pcb, q->s, ok);
+    return ok ? r : -EIO;
+}
+
+static int mq_launch_tx(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    // the transmit stage's reader protocol (tx_internal.h): ordered after a reader on another
+    // stream, both images, the counters and both FIBs mirrored on this one, the views held until
+    // the launches are enqueued; the new counters go to the table's other set
+    struct tx_dev_view v;
+    int r = tx_dev_begin(q->ipf, q->pcb, q->c->dev, q->s, &v);
+    if (r)
+        return r;
+    // blocks own contiguous runs of whole passes, at most MQ_TX_GRID_MAX of them (mq_dev_tx's rows)
+    const uint32_t passes = blocks_for(sl->n, MQ_TX_TPB);
+    const uint32_t per = (passes + MQ_TX_GRID_MAX - 1u) / MQ_TX_GRID_MAX;
+    const uint32_t grid = (passes + per - 1u) / per; // no empty block
+    MqTx w;
+    memset(&w, 0, sizeof(w));
+    w.mode = q->tx_mode;
+    w.chunk = per * MQ_TX_TPB;
+    w.ximg = v.ximg;
+    w.img = v.img;
+    w.arp = v.arp;
+    w.rt = v.rt;
+    w.ident_in = v.ident_in;
+    w.ident_out = v.ident_out;
+    w.rows = (uint32_t *)sl->d;
+    w.state = (uint32_t *)(sl->d + MQ_TX_GRID_MAX * CNDP_FWD_NETIFS * 4u);
+    hipLaunchKernelGGL(k_mq_tx_resolve, dim3(grid), dim3(MQ_TX_TPB), 0, q->s, a, w);
+    hipLaunchKernelGGL(k_mq_tx_write, dim3(grid), dim3(MQ_TX_TPB), 0, q->s, a, w);
+    const bool ok = hipGetLastError() == hipSuccess;
+    r = tx_dev_end(q->ipf, q->pcb, q->s, ok ? TX_DEV_MOVED : TX_DEV_NONE);
     return ok ? r : -EIO;
 }
 
@@ -9445,6 +9882,70 @@ static void mq_fill_udp(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32
     }
 }
 
+// ip4_output: everything the kernels need of the mbuf and its metadata, read here on the lcore
+// (k_mq_tx_resolve's comment has the words).  Zero-copy: the mbuf header and the headroom the
+// frame can take, [max(buf_addr, mtod - 42 / 34), mtod), lie in one region each, else the mbuf is
+// not taken.  Staged: the readable bytes from mtod on, copied MQ_TX_FRONT bytes into a
+// 16-byte-aligned, zero-padded place of the staging, the header's room in front of them.
+static void mq_fill_tx(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+{
+    const bool zc = q->zc != 0;
+    const uint32_t img_end = TX_IMG_END(q->tx_mode);
+    uint64_t *hoff = (uint64_t *)(sl->h + q->h_off), *hlen = (uint64_t *)(sl->h + q->h_len);
+    u32x4 *rec = (u32x4 *)(sl->h + q->h_rec);
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t j = sl->n + i;
+        const MqHdr h = mq_fill_next(sl, mbufs, i, k, zc);
+        const uint64_t up = *(const uint64_t *)(h.m + PCB_MB_USERPTR);
+        uint64_t idx = up < MQ_TX_NOIDX ? up : MQ_TX_NOIDX; // an index at or past 0xFFFF is past every vector
+        uint64_t R = h.dlen < h.room ? h.dlen : h.room, front = 0, back;
+        u32x4 r = {0u, 0u, 0u, 0u};
+        if (zc) {
+            const uint32_t hr = h.doff < img_end ? h.doff : img_end;
+            const int kf = mq_region(q, h.m, 64) < 0 ? -1 : mq_region(q, h.f - hr, hr);
+            if (kf < 0) {
+                hoff[j] = 0; // not taken
+                hlen[j] = MQ_TX_NOIDX;
+                rec[j] = r;
+                continue;
+            }
+            const MqRegion &g = q->rg[kf];
+            const uint64_t in_front = (uint64_t)(h.f - g.host), left = g.len - in_front;
+            R = R < left ? R : left;
+            front = in_front < 15u ? in_front : 15u;
+            back = left - R < 15u ? left - R : 15u;
+            hoff[j] = (uint64_t)(intptr_t)(h.f + g.delta);
+        } else {
+            R = R < q->conf.stage_max ? R : q->conf.stage_max;
+            const uint64_t span = R > 16u ? al16(R) : 16u;
+            uint8_t *dst = sl->h + q->h_stage + sl->stage_used + MQ_TX_FRONT;
+            memcpy(dst, h.f, R);
+            memset(dst + R, 0, span - R);
+            back = span - R < 15u ? span - R : 15u;
+            hoff[j] = sl->stage_used + MQ_TX_FRONT;
+            sl->stage_used += MQ_TX_FRONT + span;
+        }
+        const uint8_t *md = idx == MQ_TX_NOIDX ? nullptr : mq_md_host(q, h.m);
+        uint64_t nomd = MQ_TX_NOMD;
+        if (md) {
+            nomd = 0;
+            uint16_t fport, lport;
+            uint32_t faddr, laddr;
+            memcpy(&faddr, md + 4, 4);
+            memcpy(&laddr, md + PCB_MD_LADDR + 4, 4);
+            r.x = faddr;
+            r.y = laddr;
+            memcpy(&fport, md + 2, 2);
+            memcpy(&lport, md + PCB_MD_LADDR + 2, 2);
+            r.z = (uint32_t)fport | (uint32_t)lport << 16;
+        }
+        rec[j] = r;
+        hlen[j] = idx | (uint64_t)(h.doff < 63u ? h.doff : 63u) << MQ_TX_H_SHIFT | nomd |
+                  (uint64_t)h.dlen << MQ_TX_DLEN_SHIFT | R << MQ_TX_R_SHIFT | front << MQ_TX_FRONT_SHIFT |
+                  back << MQ_TX_BACK_SHIFT;
+    }
+}
+
 // CNDP_MQ_F_DEVICE_HEADERS: the kernels read the headers, the host hands over pointers only
 static void mq_fill_devhdr(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
 {
@@ -9846,6 +10347,53 @@ static void mq_count_ipf(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
                                                                                      : CNDP_MQ_STAT_FWD_DIRECT]++;
 }
 
+// ip4_output: the mbuf header edits of the two nodes from the device's records, zero-copy or
+// staged (tx_mbuf_apply, tx_internal.h: the text the host twin runs); staged also exactly the frame
+// bytes the kernels wrote: the header image's (tx_written) and a checksum stored behind mtod
+static void mq_wb_tx(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
+{
+    const u32x4 *rec = (const u32x4 *)(sl->h + q->h_rec);
+    const uint16_t *edw = (const uint16_t *)(sl->h + q->h_edge);
+    const uint64_t *ho = (const uint64_t *)(sl->h + q->h_off);
+    const uint32_t mode = q->tx_mode, img_end = TX_IMG_END(mode);
+    for (uint32_t i = i0; i < i1; i++) {
+        if (i + MQ_PF < i1)
+            __builtin_prefetch(sl->mb[i + MQ_PF], 1);
+        if (edw[i] == MQ_EDGE_NONE) // not taken: untouched
+            continue;
+        uint8_t *m = (uint8_t *)sl->mb[i];
+        const uint32_t rw = rec[i].w, st = (rw >> MQ_TX_REC_ST_SHIFT) & 15u;
+        if (!q->zc) {
+            const MqHdr h = mq_hdr(m); // data_off is still the one at submit
+            const uint8_t *sg = sl->h + q->h_stage + ho[i];
+            int s, e, hs, he;
+            tx_written(mode, st, edw[i] & CNDP_MQ_EDGE_TX_MASK, &s, &e, &hs, &he);
+            for (int b = s; b < e; b++)
+                if (b < hs || b >= he)
+                    h.f[b - (int)img_end] = sg[b - (int)img_end];
+            const uint32_t at = (rw >> MQ_TX_REC_CK_SHIFT) & 63u, cn = (rw >> MQ_TX_REC_CKN_SHIFT) & 3u;
+            if (at)
+                memcpy(h.f + at - 1u, sg + at - 1u, cn);
+        }
+        tx_mbuf_apply(m, mode, st);
+    }
+}
+
+static void mq_count_tx(cndp_gpu_mq_t *q, const uint16_t *ed, uint32_t k)
+{
+    for (uint32_t i = 0; i < k; i++)
+        if (ed[i] != MQ_EDGE_NONE) {
+            q->n_stat[tx_mq_stat_key(ed[i])]++;
+            if (ed[i] & CNDP_MQ_EDGE_TX_CKSUM)
+                q->n_stat[CNDP_MQ_STAT_TX_CKSUM]++;
+        }
+}
+
+// at most: the header's room, then a frame's readable bytes rounded up to 16
+static uint32_t mq_stage_tx(const struct cndp_mq_conf *k) { return MQ_TX_FRONT + ((k->stage_max + 15u) & ~15u); }
+// the blocks' rows, then a state word per mbuf
+static uint64_t mq_dev_tx(const struct cndp_mq_conf *k) { return MQ_TX_GRID_MAX * CNDP_FWD_NETIFS * 4u + al64((uint64_t)k->batch * 4u); }
+
 static uint32_t mq_stage_lookup(const struct cndp_mq_conf *k) { return (k->flags & CNDP_MQ_F_RX_PARSE) ? 32u : MQ_W4; }
 static uint32_t mq_stage_cnet(const struct cndp_mq_conf *k) { return (uint32_t)al64(k->stage_max); }
 // at most: a frame takes its readable bytes rounded up to 16
@@ -9895,6 +10443,11 @@ static const MqMode mq_modes[] = {
      .stage_of = mq_stage_udp, .len = true, .rec = 32, .rec_zc = true, .seg = 16,
      .stat_lo = CNDP_MQ_STAT_TCP_SEGMENT, .stat_hi = CNDP_MQ_STAT_TCP_IPOPT,
      .fill = mq_fill_udp, .launch = mq_launch_tcp, .wb_zc = mq_wb_tcp, .wb_staged = mq_wb_tcp},
+    // the record carries the metadata's addresses and ports in and the edge and the frame's reach out
+    {.mode = CNDP_MQ_IP4_OUTPUT, .by = MQ_BY_TX,
+     .stage_of = mq_stage_tx, .len = true, .rec = 16, .rec_zc = true, .dev_of = mq_dev_tx,
+     .stat_lo = CNDP_MQ_STAT_TX_SENT, .stat_hi = CNDP_MQ_STAT_TX_CKSUM,
+     .fill = mq_fill_tx, .launch = mq_launch_tx, .wb_zc = mq_wb_tx, .wb_staged = mq_wb_tx, .count = mq_count_tx},
 };
 
 static const MqMode *mq_mode(uint32_t mode, uint32_t by)
@@ -9993,11 +10546,12 @@ extern "C" int cndp_gpu_mq_poll_tcp(cndp_gpu_mq_t *q, void **mbufs, uint16_t *ed
 // does not count them).  The keys of a family added later are known only to the mode that counts
 // them: on every other mode they stay the unknown keys they were before that mode existed.
 static_assert(CNDP_MQ_STAT_BATCHES == 1 && CNDP_MQ_STAT_FWD_ARP_REQUEST == 10 && CNDP_MQ_STAT_L4_RECV == 11 &&
-                  CNDP_MQ_STAT_L4_NOMD == 16 && CNDP_MQ_STAT_TCP_SEGMENT == 17 && CNDP_MQ_STAT_TCP_IPOPT == 24,
+                  CNDP_MQ_STAT_L4_NOMD == 16 && CNDP_MQ_STAT_TCP_SEGMENT == 17 && CNDP_MQ_STAT_TCP_IPOPT == 24 &&
+                  CNDP_MQ_STAT_TX_SENT == 25 && CNDP_MQ_STAT_TX_CKSUM == 31,
               "cndp_gpu_mq_stat's key ranges");
 extern "C" int64_t cndp_gpu_mq_stat(const cndp_gpu_mq_t *q, int key)
 {
-    if (!q || key < CNDP_MQ_STAT_BATCHES || key > CNDP_MQ_STAT_TCP_IPOPT)
+    if (!q || key < CNDP_MQ_STAT_BATCHES || key > CNDP_MQ_STAT_TX_CKSUM)
         return -EINVAL;
     if (key <= CNDP_MQ_STAT_FWD_ARP_REQUEST || (key >= q->mode->stat_lo && key <= q->mode->stat_hi))
         return (int64_t)q->n_stat[key];

@@ -61,13 +61,7 @@
 #define TX_CK_SPLIT 8u
 #define TX_SCAN_BATCH 16u
 
-// how far a frame gets (the high byte of its state; the low byte is the netif)
-#define TXS_NONE 0u         // not taken
-#define TXS_DROP_NOUDP 1u   // udp_output's adjust failed: nothing written
-#define TXS_DROP_UDP 2u     // the IPv4 prepend failed: the UDP header is written
-#define TXS_DROP_NOROUTE 3u // no route to the source: the IPv4 header is written too
-#define TXS_DROP_IP 4u      // the Ethernet prepend failed: the same bytes
-#define TXS_OUT 5u          // ip4_output.c:93-100 ran: s_addr, type, packet_id, hdr_checksum
+// how far a frame gets is the high byte of its state (TXS_*, tx_internal.h); the low byte is the netif
 
 #define TXWL_UDP 0x100u  // in an entry's fourth word: a computed 0 goes out as 0xFFFF
 #define TXWL_ZERO 0x200u // total_length < 20: __ipv4_udptcp_cksum returns 0
@@ -586,7 +580,8 @@ struct TxFwdDev {
     int cus;
     uint32_t *img; // the forwarding table's object image, copied whole when it changed
     uint64_t gen;  // table generation mirrored (0 = none)
-    uint16_t *ident;
+    uint16_t *ident; // two sets of counters: the current one is `cur`; a reader that leaves the new
+    int cur;         // counters in the other one (TX_DEV_MOVED, the mbuf queue's kernels) swaps them
     int have_ident;
     uint16_t *state;
     uint64_t state_cap;
@@ -645,7 +640,7 @@ static int tx_ident_pull(struct cndp_fwd_tbl *t)
     HIP_TRY(hipSetDevice(d->dev));
     if (d->have_last)
         HIP_TRY(hipEventSynchronize(d->ev));
-    HIP_TRY(hipMemcpy(t->ident, d->ident, sizeof(t->ident), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t->ident, d->ident + d->cur * CNDP_FWD_NETIFS, sizeof(t->ident), hipMemcpyDeviceToHost));
     t->ident_dev_new = 0;
     return 0;
 }
@@ -654,7 +649,7 @@ static int tx_fwd_init(TxFwdDev *d)
 {
     HIP_TRY(hipDeviceGetAttribute(&d->cus, hipDeviceAttributeMultiprocessorCount, d->dev));
     const size_t rows = (size_t)d->cus * TX_BLOCKS_PER_CU;
-    HIP_TRY(hipMalloc((void **)&d->ident, CNDP_FWD_NETIFS * sizeof(uint16_t)));
+    HIP_TRY(hipMalloc((void **)&d->ident, 2u * CNDP_FWD_NETIFS * sizeof(uint16_t)));
     HIP_TRY(hipMalloc((void **)&d->bsum, rows * CNDP_FWD_NETIFS * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&d->cnt, rows * sizeof(uint32_t)));
     HIP_TRY(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming));
@@ -748,7 +743,8 @@ static int tx_mirror(TxFwdDev *fd, TxPcbDev *pd, struct cndp_fwd_tbl *ft, struct
         copied = true;
     }
     if (!fd->have_ident || ft->ident_host_new) {
-        HIP_TRY(hipMemcpyAsync(fd->ident, ft->ident, sizeof(ft->ident), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(fd->ident + fd->cur * CNDP_FWD_NETIFS, ft->ident, sizeof(ft->ident),
+                               hipMemcpyHostToDevice, s));
         copied = true;
     }
     if (copied)
@@ -760,16 +756,99 @@ static int tx_mirror(TxFwdDev *fd, TxPcbDev *pd, struct cndp_fwd_tbl *ft, struct
     return 0;
 }
 
-static int tx_run(TxFwdDev *fd, TxPcbDev *pd, struct cndp_fwd_tbl *ft, struct cndp_pcb_tbl *pt,
-                  const struct cndp_batch *b, uint32_t mode, const struct cndp_tx_io *io, hipStream_t s)
+// the reader protocol of tx_internal.h, with both locks held
+static int tx_begin_locked(TxFwdDev *fd, TxPcbDev *pd, struct cndp_fwd_tbl *ft, struct cndp_pcb_tbl *pt, hipStream_t s,
+                           struct tx_dev_view *v)
 {
     if (fd->have_last && fd->last != s)
         HIP_TRY(hipStreamWaitEvent(s, fd->ev, 0));
     if (pd->have_last && pd->last != s)
         HIP_TRY(hipStreamWaitEvent(s, pd->ev, 0));
     int r = tx_mirror(fd, pd, ft, pt, s);
-    if (r || b->n == 0)
+    if (r)
         return r;
+    FibDev arp, rt;
+    struct cndp_tbl *ta = &ft->arp_fib->t, *tr = &ft->rt4_fib->t;
+    r = fib_acquire(ta, s, &arp);
+    if (r)
+        return r;
+    r = fib_acquire(tr, s, &rt);
+    if (r) {
+        fib_release(ta);
+        return r;
+    }
+    v->ximg = pd->img;
+    v->img = fd->img;
+    v->arp = {arp.t24, arp.t8, arp.d16, arp.pages};
+    v->rt = {rt.t24, rt.t8, rt.d16, rt.pages};
+    v->ident_in = fd->ident + fd->cur * CNDP_FWD_NETIFS;
+    v->ident_out = fd->ident + (fd->cur ^ 1) * CNDP_FWD_NETIFS;
+    v->cus = fd->cus;
+    return 0;
+}
+
+extern "C" int tx_dev_begin(struct cndp_fwd_tbl *ft, struct cndp_pcb_tbl *pt, int dev, void *stream,
+                            struct tx_dev_view *v)
+{
+    pthread_mutex_lock(&ft->lock);
+    pthread_mutex_lock(&pt->lock);
+    TxFwdDev *fd = NULL;
+    TxPcbDev *pd = NULL;
+    int r = tx_fwd_get(ft, dev, &fd);
+    if (!r)
+        r = tx_pcb_get(pt, dev, &pd);
+    if (!r)
+        r = tx_begin_locked(fd, pd, ft, pt, (hipStream_t)stream, v);
+    if (r) {
+        pthread_mutex_unlock(&pt->lock);
+        pthread_mutex_unlock(&ft->lock);
+    }
+    return r;
+}
+
+static int tx_end_locked(TxFwdDev *fd, TxPcbDev *pd, struct cndp_fwd_tbl *ft, hipStream_t s, int launched)
+{
+    if (launched == TX_DEV_NONE)
+        return 0;
+    if (launched == TX_DEV_MOVED)
+        fd->cur ^= 1;
+    ft->ident_dev_new = 1;
+    fd->last = pd->last = s;
+    fd->have_last = pd->have_last = 1;
+    HIP_TRY(hipEventRecord(fd->ev, s));
+    HIP_TRY(hipEventRecord(pd->ev, s));
+    return 0;
+}
+
+extern "C" int tx_dev_end(struct cndp_fwd_tbl *ft, struct cndp_pcb_tbl *pt, void *stream, int launched)
+{
+    fib_release(&ft->rt4_fib->t);
+    fib_release(&ft->arp_fib->t);
+    const int r = tx_end_locked((TxFwdDev *)ft->xdev, (TxPcbDev *)pt->xdev, ft, (hipStream_t)stream, launched);
+    pthread_mutex_unlock(&pt->lock);
+    pthread_mutex_unlock(&ft->lock);
+    return r;
+}
+
+extern "C" int tx_dev_check(struct cndp_fwd_tbl *ft, struct cndp_pcb_tbl *pt, int dev)
+{
+    pthread_mutex_lock(&ft->lock);
+    pthread_mutex_lock(&pt->lock);
+    const TxFwdDev *fd = (const TxFwdDev *)ft->xdev;
+    const TxPcbDev *pd = (const TxPcbDev *)pt->xdev;
+    const int r = (fd && fd->dev != dev) || (pd && pd->dev != dev) ? -EINVAL : 0;
+    pthread_mutex_unlock(&pt->lock);
+    pthread_mutex_unlock(&ft->lock);
+    return r;
+}
+
+// between tx_dev_begin and tx_dev_end: *launched says whether the kernels were enqueued
+static int tx_run(TxFwdDev *fd, const struct tx_dev_view *v, const struct cndp_batch *b, uint32_t mode,
+                  const struct cndp_tx_io *io, hipStream_t s, int *launched)
+{
+    *launched = TX_DEV_NONE;
+    if (b->n == 0)
+        return 0;
     // blocks own contiguous runs of whole passes
     const uint64_t passes = ((uint64_t)b->n + TX_BLOCK - 1u) / TX_BLOCK;
     const uint64_t cap = (uint64_t)fd->cus * TX_BLOCKS_PER_CU;
@@ -812,41 +891,28 @@ static int tx_run(TxFwdDev *fd, TxPcbDev *pd, struct cndp_fwd_tbl *ft, struct cn
     a.bin_of = io->bin_of;
     a.n_bins = io->n_bins;
     a.stats = (unsigned long long *)io->stats;
-    a.ximg = pd->img;
-    a.img = fd->img;
+    a.ximg = v->ximg;
+    a.img = v->img;
+    a.arp = {v->arp.t24, v->arp.t8, v->arp.d16, v->arp.pages};
+    a.rt = {v->rt.t24, v->rt.t8, v->rt.d16, v->rt.pages};
     a.state = fd->state;
     a.bsum = fd->bsum;
-    a.ident = fd->ident;
+    a.ident = v->ident_in; // advanced in place
     a.wl = fd->wl;
     a.wl_cnt = fd->cnt;
     a.chunk = (uint32_t)chunk;
     a.grid = grid;
 
-    struct cndp_tbl *ta = &ft->arp_fib->t, *tr = &ft->rt4_fib->t;
-    r = fib_acquire(ta, s, &a.arp);
-    if (r)
-        return r;
-    r = fib_acquire(tr, s, &a.rt);
-    if (!r) {
-        hipLaunchKernelGGL(tx_resolve_kernel, dim3(grid), dim3(TX_BLOCK), 0, s, a);
-        hipLaunchKernelGGL(tx_scan_kernel, dim3(1), dim3(CNDP_FWD_NETIFS), 0, s, a);
-        hipLaunchKernelGGL(tx_write_kernel, dim3(grid), dim3(TX_BLOCK), 0, s, a);
-        hipLaunchKernelGGL(tx_cksum_kernel, dim3(grid * TX_CK_SPLIT), dim3(TX_BLOCK), 0, s, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            fprintf(stderr, "cndp_tx: launch failed: %s\n", hipGetErrorString(e));
-            r = -EIO;
-        }
-        fib_release(tr);
+    hipLaunchKernelGGL(tx_resolve_kernel, dim3(grid), dim3(TX_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tx_scan_kernel, dim3(1), dim3(CNDP_FWD_NETIFS), 0, s, a);
+    hipLaunchKernelGGL(tx_write_kernel, dim3(grid), dim3(TX_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tx_cksum_kernel, dim3(grid * TX_CK_SPLIT), dim3(TX_BLOCK), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fprintf(stderr, "cndp_tx: launch failed: %s\n", hipGetErrorString(e));
+        return -EIO;
     }
-    fib_release(ta);
-    if (r)
-        return r;
-    ft->ident_dev_new = 1;
-    HIP_TRY(hipEventRecord(fd->ev, s));
-    HIP_TRY(hipEventRecord(pd->ev, s));
-    fd->last = pd->last = s;
-    fd->have_last = pd->have_last = 1;
+    *launched = TX_DEV_INPLACE;
     return 0;
 }
 
@@ -861,20 +927,19 @@ extern "C" int cndp_gpu_ip4_output(cndp_gpu_ctx_t *ctx, cndp_fwd_tbl_t *ft, cndp
         return -EINVAL;
     const int dev = cndp_gpu_device(ctx);
     HIP_TRY(hipSetDevice(dev));
-    pthread_mutex_lock(&ft->lock);
-    pthread_mutex_lock(&pt->lock);
-    int r = 0;
-    if (io->bin_of && ((int64_t)io->n_bins <= (int64_t)fwd_max_netif(ft) || io->n_bins > 65533u))
-        r = -EINVAL;
-    TxFwdDev *fd = NULL;
-    TxPcbDev *pd = NULL;
-    if (!r)
-        r = tx_fwd_get(ft, dev, &fd);
-    if (!r)
-        r = tx_pcb_get(pt, dev, &pd);
-    if (!r)
-        r = tx_run(fd, pd, ft, pt, b, mode, io, (hipStream_t)stream);
-    pthread_mutex_unlock(&pt->lock);
-    pthread_mutex_unlock(&ft->lock);
-    return r;
+    if (io->bin_of) {
+        pthread_mutex_lock(&ft->lock);
+        const bool bad = (int64_t)io->n_bins <= (int64_t)fwd_max_netif(ft) || io->n_bins > 65533u;
+        pthread_mutex_unlock(&ft->lock);
+        if (bad)
+            return -EINVAL;
+    }
+    struct tx_dev_view v;
+    int r = tx_dev_begin(ft, pt, dev, stream, &v);
+    if (r)
+        return r;
+    int launched = TX_DEV_NONE;
+    r = tx_run((TxFwdDev *)ft->xdev, &v, b, mode, io, (hipStream_t)stream, &launched);
+    const int r2 = tx_dev_end(ft, pt, stream, launched);
+    return r ? r : r2;
 }

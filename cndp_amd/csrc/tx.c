@@ -91,7 +91,7 @@ int tx_pcb_image(struct cndp_pcb_tbl *t)
 
 /* ---- identification counters ---------------------------------------------- */
 /* call with the lock held: the host copy is what the last GPU call left */
-static int ident_current(struct cndp_fwd_tbl *t)
+int tx_ident_current(struct cndp_fwd_tbl *t)
 {
     if (t->ident_dev_new && t->xdev_ident_pull)
         return t->xdev_ident_pull(t);
@@ -103,7 +103,7 @@ int cndp_fwd_netif_ident_set(cndp_fwd_tbl_t *t, uint32_t idx, uint16_t ident)
     if (!t || idx >= CNDP_FWD_NETIFS)
         return -EINVAL;
     pthread_mutex_lock(&t->lock);
-    int r = ident_current(t);
+    int r = tx_ident_current(t);
     if (!r) {
         t->ident[idx] = ident;
         t->ident_host_new = 1;
@@ -117,7 +117,7 @@ int cndp_fwd_netif_ident_get(cndp_fwd_tbl_t *t, uint32_t idx, uint16_t *ident)
     if (!t || !ident || idx >= CNDP_FWD_NETIFS)
         return -EINVAL;
     pthread_mutex_lock(&t->lock);
-    int r = ident_current(t);
+    int r = tx_ident_current(t);
     if (!r)
         *ident = t->ident[idx];
     pthread_mutex_unlock(&t->lock);
@@ -200,7 +200,7 @@ int cndp_tx_output_host(cndp_fwd_tbl_t *ft, cndp_pcb_tbl_t *pt, uint32_t mode, v
     if (io->bin_of && ((int64_t)io->n_bins <= (int64_t)fwd_max_netif(ft) || io->n_bins > 65533u))
         r = -EINVAL;
     if (!r)
-        r = ident_current(ft);
+        r = tx_ident_current(ft);
     if (!r)
         r = tx_pcb_image(pt);
     if (r) {
@@ -312,6 +312,159 @@ int cndp_tx_output_host(cndp_fwd_tbl_t *ft, cndp_pcb_tbl_t *pt, uint32_t mode, v
     if (io->stats)
         for (int k = 0; k < CNDP_TX_NSTATS; k++)
             io->stats[k] += st[k];
+    ft->ident_host_new = 1;
+
+    if (f1 != f0)
+        pthread_mutex_unlock(&f1->t.dev_lock);
+    pthread_mutex_unlock(&f0->t.dev_lock);
+    pthread_mutex_unlock(&pt->lock);
+    pthread_mutex_unlock(&ft->lock);
+    return 0;
+}
+
+/* ---- cndp_mqtx.h: udp_output + ip4_output over mbufs on the host ------------ */
+static inline void st16(uint8_t *p, uint32_t v) /* as a little-endian host stores it */
+{
+    p[0] = (uint8_t)v;
+    p[1] = (uint8_t)(v >> 8);
+}
+static inline void st32(uint8_t *p, uint32_t v)
+{
+    st16(p, v);
+    st16(p + 2, v >> 16);
+}
+
+int cndp_ip4_output_node_host(cndp_fwd_tbl_t *ft, cndp_pcb_tbl_t *pt, uint32_t mode, void *const *mbufs, uint32_t n,
+                              uint16_t *edges, const void *readable_end, uint32_t stage_max,
+                              void *(*metadata)(const void *m))
+{
+    if (!ft || !pt || mode > CNDP_TX_IP4 || n > 256u || (n && (!mbufs || !edges)))
+        return -EINVAL;
+    pthread_mutex_lock(&ft->lock);
+    pthread_mutex_lock(&pt->lock);
+    int r = tx_ident_current(ft);
+    if (!r)
+        r = tx_pcb_image(pt);
+    if (r) {
+        pthread_mutex_unlock(&pt->lock);
+        pthread_mutex_unlock(&ft->lock);
+        return r;
+    }
+    /* the FIBs' host images are painted under their own locks, taken in address order */
+    struct cne_fib *f0 = ft->arp_fib < ft->rt4_fib ? ft->arp_fib : ft->rt4_fib;
+    struct cne_fib *f1 = ft->arp_fib < ft->rt4_fib ? ft->rt4_fib : ft->arp_fib;
+    pthread_mutex_lock(&f0->t.dev_lock);
+    if (f1 != f0)
+        pthread_mutex_lock(&f1->t.dev_lock);
+
+    const uintptr_t end = (uintptr_t)readable_end;
+    for (uint32_t i = 0; i < n; i++) {
+        uint8_t *m = (uint8_t *)mbufs[i];
+        edges[i] = (uint16_t)CNDP_TX_EDGE_NONE;
+        if (!m || (end && (uintptr_t)m + 64u > end))
+            continue;
+        uint64_t buf, up;
+        uint16_t H, blen, dlen0;
+        memcpy(&buf, m + PCB_MB_BUF_ADDR, 8);
+        memcpy(&up, m + PCB_MB_USERPTR, 8);
+        memcpy(&H, m + PCB_MB_DATA_OFF, 2);
+        memcpy(&blen, m + PCB_MB_BUF_LEN, 2);
+        memcpy(&dlen0, m + PCB_MB_DATA_LEN, 2);
+        uint8_t *const f = (uint8_t *)((uintptr_t)buf + H); /* mtod at submit */
+        if (end && (uintptr_t)f > end)
+            continue;
+        const uint32_t w = up < pt->count ? pt->ximg[TXI_HDR + up] : 0u;
+        uint8_t *md = NULL;
+        if (w & TXW_LIVE)
+            md = metadata ? (uint8_t *)metadata(m) : m + 64;
+        uint32_t st = tx_reach_front(w, md == NULL, mode, H);
+        if (st == TXS_NONE)
+            continue;
+        uint32_t edge = CNDP_TX_EDGE_PKT_DROP, proto_drop = 0, cksum = 0;
+        uint32_t src = 0, dst = 0, U0 = 0, U1 = 0, rw = 0;
+        const uint32_t proto = w & 0xffu, total = tx_total(mode, dlen0);
+        uint8_t *l4 = f, *ip;
+        if (st != TXS_NOMD) {
+            uint16_t fport, lport;
+            memcpy(&dst, md + 4, 4);
+            memcpy(&src, md + PCB_MD_LADDR + 4, 4);
+            memcpy(&fport, md + 2, 2);
+            memcpy(&lport, md + PCB_MD_LADDR + 2, 2);
+            if (mode == CNDP_TX_UDP && st != TXS_DROP_NOUDP) { /* udp_output */
+                l4 = f - 8;
+                U0 = (uint32_t)lport | (uint32_t)fport << 16; /* src_port = lport, dst_port = fport */
+                U1 = tx_step((dlen0 + 8u) & 0xffffu);          /* dgram_len, dgram_cksum = 0 */
+                st32(l4, U0);
+                st32(l4 + 4, U1);
+            }
+        }
+        if (st == TX_ROUTE) { /* ip4_output: the header but for packet_id, then the route */
+            ip = l4 - 20;
+            const uint32_t w0 = 0x45u | ((w >> 16) & 0xffu) << 8 | tx_step(total) << 16;
+            const uint32_t w2 = ((w >> 8) & 0xffu) | proto << 8; /* ttl, proto, hdr_checksum = 0 */
+            st32(ip, w0);
+            st16(ip + 6, 0);
+            st32(ip + 8, w2);
+            st32(ip + 12, src);
+            st32(ip + 16, dst);
+            const uint32_t ri = lpm4(ft->rt4_fib, __builtin_bswap32(src)) & 0xffffffu;
+            if (ri < ft->rt_cap)
+                rw = fwd_rt(ft)[2u * (size_t)ri + 1u];
+            st = tx_reach_route(rw, mode, H);
+            if (st == TXS_OUT) {
+                uint8_t *eth = ip - 14;
+                const uint32_t nif = rw & 0xffu;
+                const uint32_t *mac = fwd_netif(ft) + 2u * (size_t)nif;
+                st32(eth + 6, mac[0]);
+                st16(eth + 10, mac[1]);
+                st16(eth + 12, 0x0008u);
+                const uint32_t id = ft->ident[nif];
+                st16(ip + 4, swap16(id));
+                ft->ident[nif] = (uint16_t)(id + tx_step(total)); /* += ip->total_length as loaded */
+                const uint32_t hs = (w0 & 0xffffu) + (w0 >> 16) + swap16(id) + (w2 & 0xffffu) + (src & 0xffffu) +
+                                    (src >> 16) + (dst & 0xffffu) + (dst >> 16);
+                st16(ip + 10, ~reduce(hs) & 0xffffu);
+                cksum = proto == 17u ? (w & TXW_CKSUM) != 0 : proto == 6u;
+                proto_drop = proto != 17u && proto != 6u;
+                if (cksum) {
+                    /* the readable L4 bytes from mtod on: data_len clipped at the buffer's end, the
+                     * region's and stage_max; the rest read as zero and are never written */
+                    uint32_t R = dlen0;
+                    const uint32_t room = blen > H ? (uint32_t)(blen - H) : 0u;
+                    R = R < room ? R : room;
+                    if (end && end - (uintptr_t)f < R)
+                        R = (uint32_t)(end - (uintptr_t)f);
+                    if (stage_max && stage_max < R)
+                        R = stage_max;
+                    const uint32_t hdr = mode == CNDP_TX_UDP ? 8u : 0u;
+                    const uint32_t l4_len = total >= 20u ? total - 20u : 0u;
+                    uint32_t body = l4_len > hdr ? l4_len - hdr : 0u, S = 0;
+                    body = body < R ? body : R;
+                    for (uint32_t k = 0; k < body; k++)
+                        S += (k & 1u) ? (uint32_t)f[k] << 8 : (uint32_t)f[k];
+                    if (hdr)
+                        S += tx_udp_hdr_sum(U0, U1, l4_len);
+                    const uint32_t c = tx_l4_cksum(S, total, proto, src, dst);
+                    const uint32_t at = proto == 17u ? 6u : 16u; /* from the L4 start */
+                    for (uint32_t k = 0; k < 2u; k++)
+                        if (at + k < hdr + R)
+                            l4[at + k] = (uint8_t)(c >> (8u * k));
+                }
+                if (!proto_drop) {
+                    edge = CNDP_TX_EDGE_ARP_REQUEST;
+                    const uint32_t ai = lpm4(ft->arp_fib, __builtin_bswap32(dst)) & 0xffffffu;
+                    const uint32_t *arp = ai < ft->arp_cap ? fwd_arp(ft) + 2u * (size_t)ai : NULL;
+                    if (arp && (arp[0] & FWD_SET)) {
+                        st16(eth, arp[0]);
+                        st32(eth + 2, arp[1]);
+                        edge = nif + CNDP_TX_EDGE_OUTPUT; /* the route's netif, not the ARP entry's */
+                    }
+                }
+            }
+        }
+        tx_mbuf_apply(m, mode, st);
+        edges[i] = (uint16_t)tx_mq_edge(st, edge, proto_drop, cksum);
+    }
     ft->ident_host_new = 1;
 
     if (f1 != f0)

@@ -114,7 +114,7 @@ class MbufQueue:
     def __init__(self, cl, mode: int, flags: int = 0, batch: int = 8192, depth: int = 4,
                  max_delay_us: int = 50, umem=None, lport: int = 0, stage_max: int = 0, metadata=None,
                  fib=None, acl=None, acl_mode: int = N.CNDP_ACL_STRICT, acl_flags: int = 0, lports=(),
-                 fwd_tbl=None, pcb_tbl=None):
+                 fwd_tbl=None, pcb_tbl=None, tx_mode: int = N.CNDP_TX_UDP):
         """metadata: cnet's pktmbuf_metadata hook, a Python function of the mbuf
         address returning the metadata address (None: m + 64).
         cndpfwd modes (CNDP_MQ_CFWD_FWD / _L3FWD / CNDP_MQ_ACL_FWD, cndp_mqfwd.h):
@@ -127,7 +127,10 @@ class MbufQueue:
         udp_input demultiplex in; it must outlive the queue.  metadata is the
         hook poll calls (returning 0 / None stands for NULL).
         CNDP_MQ_TCP_INPUT (cndp_mqtcp.h): pcb_tbl is the TCP PcbTable tcp_input
-        looks connections up in; the create call is chosen by the mode."""
+        looks connections up in; the create call is chosen by the mode.
+        CNDP_MQ_IP4_OUTPUT (cndp_mqtx.h): fwd_tbl and pcb_tbl are the tables
+        udp_output + ip4_output resolve in, tx_mode is CNDP_TX_UDP or
+        CNDP_TX_IP4; metadata is the hook submit calls."""
         self._L = N.lib()
         self._keep = (fib, acl, fwd_tbl, pcb_tbl)
         c = N.MqConf()
@@ -149,6 +152,11 @@ class MbufQueue:
                 w.lport_mask[k] = bits
             N.check(self._L.cndp_gpu_mq_create_fwd(cl.h, ctypes.byref(c), ctypes.byref(w), ctypes.byref(h)),
                     "cndp_gpu_mq_create_fwd")
+        elif mode == N.CNDP_MQ_IP4_OUTPUT:
+            N.check(self._L.cndp_gpu_mq_create_ip4_output(cl.h, ctypes.byref(c),
+                                                          fwd_tbl.h if fwd_tbl is not None else None,
+                                                          pcb_tbl.h if pcb_tbl is not None else None, tx_mode,
+                                                          ctypes.byref(h)), "cndp_gpu_mq_create_ip4_output")
         elif fwd_tbl is not None:
             N.check(self._L.cndp_gpu_mq_create_ip4_forward(cl.h, ctypes.byref(c), fwd_tbl.h, ctypes.byref(h)),
                     "cndp_gpu_mq_create_ip4_forward")

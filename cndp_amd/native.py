@@ -2,7 +2,8 @@
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
 include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h,
 include/cndp_acl.h, include/cndp_cfwd.h, include/cndp_mqfwd.h,
-include/cndp_mqcnet.h, include/cndp_mql4.h and include/cndp_mqtcp.h).
+include/cndp_mqcnet.h, include/cndp_mql4.h, include/cndp_mqtcp.h and
+include/cndp_mqtx.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -169,6 +170,17 @@ CNDP_MQ_EDGE_TCP_IPOPT = 0x0040
 CNDP_MQ_EDGE_TCP_MASK = 0xFF3F
 (CNDP_MQ_STAT_TCP_SEGMENT, CNDP_MQ_STAT_TCP_NOMATCH, CNDP_MQ_STAT_TCP_CKSUM, CNDP_MQ_STAT_TCP_NOMD,
  CNDP_MQ_STAT_TCP_ADJUST, CNDP_MQ_STAT_TCP_SHORT, CNDP_MQ_STAT_TCP_BADOFF, CNDP_MQ_STAT_TCP_IPOPT) = range(17, 25)
+# cndp_mqtx.h
+CNDP_MQ_IP4_OUTPUT = 10
+CNDP_MQ_EDGE_TX_MASK = 0x01FF
+CNDP_MQ_EDGE_TX_CKSUM = 0x1000
+CNDP_MQ_TX_CAUSE_NOMD, CNDP_MQ_TX_CAUSE_HEADROOM, CNDP_MQ_TX_CAUSE_NOROUTE, CNDP_MQ_TX_CAUSE_PROTO = 1, 2, 3, 4
+(CNDP_MQ_STAT_TX_SENT, CNDP_MQ_STAT_TX_ARP_REQUEST, CNDP_MQ_STAT_TX_DROP_NOMD, CNDP_MQ_STAT_TX_DROP_HEADROOM,
+ CNDP_MQ_STAT_TX_DROP_NOROUTE, CNDP_MQ_STAT_TX_DROP_PROTO, CNDP_MQ_STAT_TX_CKSUM) = range(25, 32)
+
+
+def CNDP_MQ_EDGE_TX_CAUSE(e: int) -> int:
+    return (e >> 9) & 7
 
 
 def CNDP_MQ_EDGE(node: int, e: int) -> int:
@@ -472,6 +484,11 @@ def lib():
         "cndp_gpu_mq_poll_tcp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
         "cndp_tcp_input_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32,
                                              c_void_p]),
+        # cndp_mqtx.h
+        "cndp_gpu_mq_create_ip4_output": (c_int, [c_void_p, POINTER(MqConf), c_void_p, c_void_p, c_uint32,
+                                                  POINTER(c_void_p)]),
+        "cndp_ip4_output_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p,
+                                              c_uint32, c_void_p]),
         # cndp_tx.h
         "cndp_pcb_tx_set": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
         "cndp_pcb_tx_get": (c_int, [c_void_p, c_uint32, POINTER(PcbTx)]),
@@ -512,7 +529,8 @@ def exported_symbols():
     import re
     names = []
     inc = os.path.join(os.path.dirname(HERE), "include")
-    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h", "cndp_mqcnet.h", "cndp_mql4.h", "cndp_mqtcp.h"):
+    for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h", "cndp_mqcnet.h", "cndp_mql4.h", "cndp_mqtcp.h",
+              "cndp_mqtx.h"):
         with open(os.path.join(inc, h)) as f:
             txt = f.read()
         names += re.findall(r"^[A-Za-z_][\w \*]*?\b((?:cne|cndp|ip4)_\w+)\s*\(", txt, re.M)

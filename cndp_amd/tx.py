@@ -97,3 +97,20 @@ def output_host(fwd_table, pcb_table, slab: np.ndarray, n: int, pcb, faddr, ladd
             "cndp_tx_output_host")
     out["n_bins"] = n_bins
     return out
+
+
+def ip4_output_node_host(fwd_table, pcb_table, ptrs, n: int | None = None, tx_mode: int = N.CNDP_TX_UDP,
+                         readable_end: int = 0, stage_max: int = 0, metadata=None) -> np.ndarray:
+    """cndp_ip4_output_node_host (include/cndp_mqtx.h): udp_output + ip4_output on
+    the calling thread over one burst of mbuf pointers (a ctypes array, as
+    MbufPool.ptrs returns); the mbufs and their frames are rewritten in place.
+    metadata: a Python function of the mbuf address returning the metadata
+    address (None: m + 64).  Returns the edges."""
+    n = len(ptrs) if n is None else n
+    edges = np.zeros(max(n, 1), np.uint16)[:n]
+    fn = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p)(metadata) if metadata else None
+    N.check(N.lib().cndp_ip4_output_node_host(fwd_table.h, pcb_table.h, tx_mode, ptrs, n, edges.ctypes.data,
+                                              readable_end or None, stage_max,
+                                              ctypes.cast(fn, ctypes.c_void_p) if fn else None),
+            "cndp_ip4_output_node_host")
+    return edges

@@ -29,6 +29,8 @@
  *    carries frames, not mbufs; a sent frame starts data_off - 42 (UDP mode) or
  *    data_off - 34 (IP4 mode) bytes into its buffer;
  *  - arp_request itself, eth_tx and the channel callback.
+ * Over pktmbuf_t bursts, with md == NULL and the bookkeeping, the same rule is a
+ * mode of the mbuf queue: cndp_mqtx.h.
  * Where the reference's behaviour is undefined this build defines it:
  *  - a frame whose pcb[i] is CNDP_PCB_NONE, at or past the vector's length or a
  *    deleted entry is not taken (the reference dereferences m->userptr);
