@@ -40,6 +40,8 @@
 #include "pcb_internal.h"           // the udp_input and tcp_input queue modes' per-frame rules and their tables' reader protocols
 #include "../../include/cndp_mql4.h"
 #include "../../include/cndp_mqtcp.h"
+#include "tcb_internal.h"           // the tcp_segment queue mode's per-segment rule and its table's reader protocol
+#include "../../include/cndp_mqtcb.h"
 #include "tx_internal.h"            // the ip4_output queue mode's per-mbuf rule and its tables' reader protocol
 
 #define CNDP_VERSION "cndp_amd 0.1 (gfx950)"
@@ -8031,7 +8033,23 @@ static int mq_udp_lds_init(void)
 // mbuf's lengths from it (mq_wb_tcp).
 #define MQ_TCP_NOIDX 0xFFFFu
 
-__global__ __launch_bounds__(MQ_TPB) void k_mq_tcp_input(MqArgs a, const uint32_t *__restrict__ img)
+// CNDP_MQ_TCP_SEGMENT's (cndp_mqtcb.h) share of a slot's device block: what its first launch
+// leaves for its second
+struct MqTseg {
+    uint32_t *first;   // CNDP_PART_BINS_MAX words, 0xFFFFFFFF at launch: per PCB index the lowest judged mbuf
+    u32x4 *keep;       // 3 per mbuf: the two record halves, {frame address lo, hi, R | l3 << 16, edge | judged << 16}
+    const u32x4 *tcb;  // the TCB image's mirror: 3 x 16 bytes per PCB index
+    uint32_t cap;      // its entries
+    uint32_t now;
+};
+#define MQ_TSEG_BITS_SHIFT 40u // the frame word's TCB_MQ_* bits (mq_fill_tseg)
+
+// SEG: CNDP_MQ_TCP_SEGMENT's first launch.  The same walk; its lanes also decide which mbufs the
+// second launch judges (tcb_mq_judged_dev, tcb_internal.h), take the minimum of their indices per
+// PCB -- a minimum does not depend on the order the lanes arrive in -- and leave record, frame
+// address and edge in device memory instead of pinned memory; the second launch completes the slot.
+template <bool SEG>
+__device__ __forceinline__ void mq_tcp_input_body(const MqArgs &a, const uint32_t *__restrict__ img, const MqTseg &w)
 {
     const uint32_t lane = threadIdx.x, gl = lane & 15u, grp = lane >> 4;
     const uint32_t flags = img[2];
@@ -8040,13 +8058,15 @@ __global__ __launch_bounds__(MQ_TPB) void k_mq_tcp_input(MqArgs a, const uint32_
         const uint32_t i = base + lane;
         const bool live = i < a.n;
         const uint8_t *p = nullptr;
-        uint32_t R = 0, l3 = 0, front = 0, back = 0;
+        uint32_t R = 0, l3 = 0, front = 0, back = 0, bits = 0;
         if (live) {
             const uint64_t pv = a.priv[i], o = a.off[i];
             l3 = (uint32_t)pv & 0x1ffu;
             R = (uint32_t)(pv >> MQ_UDP_R_SHIFT) & 0xffffu;
             front = (uint32_t)(pv >> MQ_UDP_FRONT_SHIFT) & 15u;
             back = (uint32_t)(pv >> MQ_UDP_BACK_SHIFT) & 15u;
+            if (SEG)
+                bits = (uint32_t)(pv >> MQ_TSEG_BITS_SHIFT) & 7u;
             if (!a.zc)
                 p = o <= a.slab_len && R <= a.slab_len - o ? a.slab + o : nullptr; // never from mq_fill_udp
             else
@@ -8157,9 +8177,86 @@ __global__ __launch_bounds__(MQ_TPB) void k_mq_tcp_input(MqArgs a, const uint32_
             s.y = sg[1];
             s.z = sg[2];
             s.w = sg[3];
-            a.rec[2u * i] = r;
-            a.rec[2u * i + 1u] = s;
-            a.edges[i] = (uint16_t)edge;
+            if (SEG) {
+                const bool judged = taken && idx < w.cap && tcb_mq_judged_dev(edge, bits, sg[3] >> 24, tot);
+                if (judged) // idx < cap <= CNDP_PART_BINS_MAX
+                    atomicMin(&w.first[idx], i);
+                u32x4 x;
+                x.x = (uint32_t)(uintptr_t)p;
+                x.y = (uint32_t)((uint64_t)(uintptr_t)p >> 32);
+                x.z = R | l3 << 16;
+                x.w = (edge & 0xffffu) | (judged ? 1u << 16 : 0u);
+                w.keep[3u * i] = r;
+                w.keep[3u * i + 1u] = s;
+                w.keep[3u * i + 2u] = x;
+            } else {
+                a.rec[2u * i] = r;
+                a.rec[2u * i + 1u] = s;
+                a.edges[i] = (uint16_t)edge;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MQ_TPB) void k_mq_tcp_input(MqArgs a, const uint32_t *__restrict__ img)
+{
+    mq_tcp_input_body<false>(a, img, MqTseg{});
+    mq_complete(a);
+}
+
+// CNDP_MQ_TCP_SEGMENT (cndp_mqtcb.h), two launches a batch on the queue's stream.  The first is
+// k_mq_tcp_input's walk (above).  The second, k_mq_tcp_segment, has one mbuf per lane and reads
+// nothing of the slot's pinned words again: record, frame address, readable bytes and edge come
+// from the slot's device block.  A judged lane gathers its PCB's 48-byte TCB entry as three
+// 16-byte loads from the mirror (at most 192 KiB, L2-resident) and the word first[pcb] with
+// them; a segment with options reads them through the bounded byte reader -- 4 dwords when the
+// header is 32 bytes or less, 11 otherwise -- into registers, and tcb_segment() (tcb_internal.h,
+// the text the twin compiles) walks them there by a chain of selects: no indexed register file,
+// no scratch, no LDS.  Every lane writes its mbuf's 64-byte record -- mode 9's 32 bytes, opt,
+// the verdict -- and its edge to pinned memory; mq_complete raises the slot's flag.
+__global__ __launch_bounds__(MQ_TPB) void k_mq_tseg_input(MqArgs a, const uint32_t *__restrict__ img, MqTseg w)
+{
+    mq_tcp_input_body<true>(a, img, w);
+}
+
+__global__ __launch_bounds__(MQ_TPB) void k_mq_tcp_segment(MqArgs a, MqTseg w)
+{
+    for (uint32_t base = blockIdx.x * MQ_TPB; base < a.n; base += gridDim.x * MQ_TPB) {
+        const uint32_t i = base + threadIdx.x;
+        if (i < a.n) {
+            const u32x4 r = w.keep[3u * i], s = w.keep[3u * i + 1u], x = w.keep[3u * i + 2u];
+            uint32_t o[4] = {0u, 0u, 0u, 0u}, v = CNDP_TCPSEG_NONE;
+            if (x.w >> 16) { // judged: r.x's index is below cap
+                const uint32_t idx = r.x & 0xffffu;
+                const u32x4 *tp = w.tcb + (size_t)idx * 3u;
+                const u32x4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
+                const uint32_t fi = w.first[idx]; // with the gather, not behind the parse
+                const uint32_t e[TCB_WORDS] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
+                const uint8_t *p = (const uint8_t *)(uintptr_t)((uint64_t)x.x | (uint64_t)x.y << 32);
+                const uint32_t R = x.z & 0xffffu, at = (x.z >> 16) + TCB_HDR_LEN, offset = s.w >> 24;
+                uint32_t wd[TCB_OPT_WORDS];
+#pragma unroll
+                for (uint32_t k = 0; k < TCB_OPT_WORDS; k++)
+                    wd[k] = 0u;
+                if (offset > TCB_HDR_LEN) { // bytes at or past R read as zero: the read at opt_end too
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; k++)
+                        wd[k] = mqf_le32(p, R, at + 4u * k);
+                    if (offset > 32u) {
+#pragma unroll
+                        for (uint32_t k = 4u; k < TCB_OPT_WORDS; k++)
+                            wd[k] = mqf_le32(p, R, at + 4u * k);
+                    }
+                }
+                v = tcb_segment(e, s.x, s.y, s.z & 0xffffu, s.w & 0xffffu, (s.w >> 16) & 0xffu, offset, wd, w.now, o);
+                if (fi == i)
+                    v |= CNDP_TCPSEG_FIRST;
+            }
+            a.rec[4u * i] = r;
+            a.rec[4u * i + 1u] = s;
+            a.rec[4u * i + 2u] = u32x4{o[0], o[1], o[2], o[3]};
+            a.rec[4u * i + 3u] = u32x4{v, 0u, 0u, 0u};
+            a.edges[i] = (uint16_t)x.w;
         }
     }
     mq_complete(a);
@@ -8865,6 +8962,7 @@ typedef void (*mq_wb_fn)(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
 #define MQ_BY_UDP 3u   // cndp_gpu_mq_create_udp_input
 #define MQ_BY_TCP 4u   // cndp_gpu_mq_create_tcp_input
 #define MQ_BY_TX 5u    // cndp_gpu_mq_create_ip4_output
+#define MQ_BY_TSEG 6u  // cndp_gpu_mq_create_tcp_segment
 #define MQ_FIB4 1u
 #define MQ_FIB6 2u
 struct MqMode {
@@ -8878,9 +8976,10 @@ struct MqMode {
     uint32_t (*stage_of)(const struct cndp_mq_conf *k); // ... or, where the conf decides, this
     uint32_t wb_span;  // staged: the frame's first bytes the kernel may change (mq_wb_span copies them back)
     bool len;          // the h_len array exists
-    uint32_t rec;      // record bytes per mbuf (0, 8, 16, 32), staged and with host writeback ...
+    uint32_t rec;      // record bytes per mbuf (0, 8, 16, 32, 64), staged and with host writeback ...
     bool rec_zc;       // ... and zero-copy as well
     uint32_t seg;      // where in the record a struct cndp_tcp_seg lies for cndp_gpu_mq_poll_tcp (0: the mode has none)
+    uint32_t opt;      // ... and a struct cndp_tcp_opt, the verdict's word behind it, for cndp_gpu_mq_poll_tcpseg (0: none)
     bool md;           // cnet_metadata: its addresses at h_md (zero-copy), the records' at h_rmd (host writeback)
     bool bst;          // the h_bst array exists ...
     uint32_t bst_flag; // ... or exists with this flag
@@ -8889,7 +8988,9 @@ struct MqMode {
     bool spec;         // the launch runs the context's ptype speculation: reset when a launch fails,
                        // its error taken when a batch completes
     uint64_t (*dev_of)(const struct cndp_mq_conf *k); // optional: the bytes of device memory its kernels keep per slot
-    int stat_lo, stat_hi; // the CNDP_MQ_STAT_* keys the mode counts (0, 0: none)
+    uint64_t (*pin_of)(const struct cndp_mq_conf *k); // optional: pinned bytes of its own per slot, at h_own
+    int stat_lo, stat_hi;   // the CNDP_MQ_STAT_* keys the mode counts (0, 0: none) ...
+    int stat2_lo, stat2_hi; // ... and a second range of them (0, 0: none)
     // the per-burst header walk into the open slot (room checked by the caller); fill_devhdr: with
     // CNDP_MQ_F_DEVICE_HEADERS, pointers only (nullptr: the mode ignores the flag)
     mq_fill_fn fill, fill_devhdr;
@@ -8921,7 +9022,7 @@ struct cndp_gpu_mq {
     uint32_t *flags, *flags_d;     // pinned completion flags (host / device view)
     uint32_t *tickets;             // device, one per slot
     // byte offsets inside each slot's pinned block (H) and device block (D)
-    uint64_t h_mb, h_off, h_len, h_md, h_edge, h_rec, h_rmd, h_stage, h_bst, h_bytes;
+    uint64_t h_mb, h_off, h_len, h_md, h_edge, h_rec, h_rmd, h_stage, h_bst, h_own, h_bytes;
     int hostwb;                    // zc cnet / ip4_lookup with CNDP_MQ_F_HOST_WRITEBACK
     uint64_t d_nh, d_edge, d_pt, d_rm, d_hash, d_ipl, d_win, d_off, d_len, d_md, d_bytes;
     int devhdr;                    // zc with CNDP_MQ_F_DEVICE_HEADERS (ip4_lookup, cnet)
@@ -8934,12 +9035,15 @@ struct cndp_gpu_mq {
     int err;                       // a launch error not yet reported (returned by the next submit)
     // cndp_gpu_mq_stat's counters by CNDP_MQ_STAT_* key: batches and mbufs launched so far, and the
     // mode's own, counted by poll
-    uint64_t n_stat[CNDP_MQ_STAT_TX_CKSUM + 1];
+    uint64_t n_stat[CNDP_MQ_STAT_TSEG_PRED_NONE + 1];
     struct cndp_mq_fwd fwd;        // cndpfwd modes (cndp_gpu_mq_create_fwd): the tables and the known ports
     cndp_fwd_tbl_t *ipf;           // CNDP_MQ_IP4_FORWARD (cndp_gpu_mq_create_ip4_forward) and CNDP_MQ_IP4_OUTPUT
                                    // (cndp_gpu_mq_create_ip4_output): the forwarding table
     cndp_pcb_tbl_t *pcb;           // CNDP_MQ_UDP_INPUT (cndp_gpu_mq_create_udp_input), CNDP_MQ_TCP_INPUT
-                                   // (cndp_gpu_mq_create_tcp_input) and CNDP_MQ_IP4_OUTPUT: the PCB table
+                                   // (cndp_gpu_mq_create_tcp_input), CNDP_MQ_TCP_SEGMENT and CNDP_MQ_IP4_OUTPUT:
+                                   // the PCB table
+    cndp_tcb_tbl_t *tcb;           // CNDP_MQ_TCP_SEGMENT (cndp_gpu_mq_create_tcp_segment): the TCB table ...
+    uint32_t tcp_now;              // ... and cndp_gpu_mq_tcp_now's value
     uint32_t tx_mode;              // CNDP_MQ_IP4_OUTPUT: CNDP_TX_UDP or CNDP_TX_IP4
     MqSlot slot[CNDP_MQ_DEPTH_MAX];
 };
@@ -9001,7 +9105,8 @@ static void mq_layout(cndp_gpu_mq_t *q)
     q->h_rmd = q->h_rec + (rec ? al64(B * m->rec) : 0);   // host writeback: the records' metadata addresses
     q->h_stage = q->h_rmd + (m->md && q->hostwb ? B * 32 : 0);
     q->h_bst = q->h_stage + B * q->stage;                 // what the mode's burst hook keeps per burst
-    q->h_bytes = q->h_bst + (m->bst || (k.flags & m->bst_flag) ? al64((B + 1) * 4) : 0);
+    q->h_own = q->h_bst + (m->bst || (k.flags & m->bst_flag) ? al64((B + 1) * 4) : 0);
+    q->h_bytes = q->h_own + (m->pin_of ? al64(m->pin_of(&k)) : 0);
     q->d_nh = 0;
     q->d_edge = q->d_nh + al64(B * 4);
     q->d_pt = q->d_edge + al64(B);
@@ -9189,6 +9294,27 @@ extern "C" int cndp_gpu_mq_create_tcp_input(cndp_gpu_ctx_t *c, const struct cndp
     if (r)
         return r;
     return mq_create(c, conf, MQ_BY_TCP, nullptr, nullptr, tbl, out);
+}
+
+// cndp_mqtcb.h: tcp_input, tcp_do_options and the prediction tests over a TCP PCB table and its TCB table
+extern "C" int cndp_gpu_mq_create_tcp_segment(cndp_gpu_ctx_t *c, const struct cndp_mq_conf *conf, cndp_pcb_tbl_t *tbl,
+                                              cndp_tcb_tbl_t *tcbs, cndp_gpu_mq_t **out)
+{
+    if (!c || !conf || !tbl || !tcbs || !out)
+        return -EINVAL;
+    *out = nullptr;
+    const MqMode *m = mq_mode(conf->mode, MQ_BY_TSEG);
+    if (!m || (conf->flags & ~m->flags) || tcbs->pcb != tbl)
+        return -EINVAL;
+    int r = pcb_tdev_check(tbl, c->dev); // one table, one device, as cndp_gpu_tcp_input ...
+    if (!r)
+        r = tcb_dev_check(tcbs, c->dev); // ... and cndp_gpu_tcp_segment have it
+    if (r)
+        return r;
+    r = mq_create(c, conf, MQ_BY_TSEG, nullptr, nullptr, tbl, out);
+    if (!r)
+        (*out)->tcb = tcbs;
+    return r;
 }
 
 // cndp_mqtx.h: cnet's udp_output + ip4_output nodes over a forwarding table and a PCB table
@@ -9403,6 +9529,43 @@ static int mq_launch_tcp(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
     const bool ok = hipGetLastError() == hipSuccess;
     r = pcb_tdev_end(q->pcb, q->s, ok);
     return ok ? r : -EIO;
+}
+
+#define MQ_TSEG_FIRST_BYTES (CNDP_PART_BINS_MAX * 4u) // first[]: the head of the slot's device block
+static uint64_t mq_dev_tseg(const struct cndp_mq_conf *k) { return MQ_TSEG_FIRST_BYTES + (uint64_t)k->batch * 48u; }
+// the snapshot of changed TCB entries a launch copies from (tcb_dev_begin's staging)
+static uint64_t mq_pin_tseg(const struct cndp_mq_conf *) { return (uint64_t)CNDP_PCB_MAX_ENTRIES * TCB_WORDS * 4u; }
+static_assert(CNDP_PCB_MAX_ENTRIES <= CNDP_PART_BINS_MAX && CNDP_PCB_MAX_ENTRIES <= MQ_TCP_NOIDX, "first[] and the record's index field");
+
+static int mq_launch_tseg(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
+{
+    // both mirrors' reader protocols, the TCB table's lock outside the PCB table's (tcb_internal.h,
+    // pcb_internal.h): ordered after a reader on another stream, the images mirrored on this one,
+    // our end recorded for the next reader.  Changed TCBs are snapshot into this slot's pinned
+    // block and copied from there: the launch does not wait for the stream.
+    const uint32_t *timg = nullptr, *img = nullptr;
+    int r = tcb_dev_begin(q->tcb, q->c->dev, q->s, sl->h + q->h_own, &timg);
+    if (r)
+        return r;
+    if ((r = pcb_tdev_begin(q->pcb, q->c->dev, q->s, &img))) {
+        (void)tcb_dev_end(q->tcb, q->s, 0);
+        return r;
+    }
+    MqTseg w;
+    w.first = (uint32_t *)sl->d;
+    w.keep = (u32x4 *)(sl->d + MQ_TSEG_FIRST_BYTES);
+    w.tcb = (const u32x4 *)timg;
+    w.cap = q->tcb->cap;
+    w.now = q->tcp_now;
+    bool ok = hipMemsetAsync(sl->d, 0xff, MQ_TSEG_FIRST_BYTES, q->s) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_mq_tseg_input, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, img, w);
+        hipLaunchKernelGGL(k_mq_tcp_segment, dim3(mq_grid(sl)), dim3(MQ_TPB), 0, q->s, a, w);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    r = pcb_tdev_end(q->pcb, q->s, ok);
+    const int r2 = tcb_dev_end(q->tcb, q->s, ok);
+    return ok ? (r ? r : r2) : -EIO;
 }
 
 static int mq_launch_tx(cndp_gpu_mq_t *q, MqSlot *sl, MqArgs &a)
@@ -9847,7 +10010,9 @@ static void mq_fill_ipf(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32
 // the readable bytes: data_len clipped at the buffer's end, then at the frame's
 // region's end (zero-copy) or at stage_max (staged, copied into a 16-byte-aligned,
 // zero-padded place of the staging); front / back: what an aligned load may overhang
-static void mq_fill_udp(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k)
+// tseg: CNDP_MQ_TCP_SEGMENT's words (mq_fill_tseg)
+static inline __attribute__((always_inline)) void mq_fill_l4(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k,
+                                                            const bool tseg)
 {
     const bool zc = q->zc != 0;
     uint64_t *hoff = (uint64_t *)(sl->h + q->h_off), *hlen = (uint64_t *)(sl->h + q->h_len);
@@ -9879,8 +10044,18 @@ static void mq_fill_udp(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32
             sl->stage_used += span;
         }
         hlen[j] = l3 | R << MQ_UDP_R_SHIFT | front << MQ_UDP_FRONT_SHIFT | back << MQ_UDP_BACK_SHIFT;
+        if (tseg) // what decides the mbuf's final edge and only the lcore knows
+            hlen[j] |= (uint64_t)tcb_mq_host_bits(mq_md_host(q, h.m) == nullptr, l3, h.doff, h.blen, h.dlen)
+                       << MQ_TSEG_BITS_SHIFT;
     }
 }
+
+static void mq_fill_udp(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k) { mq_fill_l4(q, sl, mbufs, k, false); }
+
+// CNDP_MQ_TCP_SEGMENT: mq_fill_udp's words, and in bits 40-42 of the h_len word the TCB_MQ_* bits
+// (tcb_internal.h), the metadata hook called here as mq_fill_tx calls it: with them the kernels
+// know which mbufs poll will drop, and FIRST lands on the first one that survives
+static void mq_fill_tseg(cndp_gpu_mq_t *q, MqSlot *sl, void *const *mbufs, uint32_t k) { mq_fill_l4(q, sl, mbufs, k, true); }
 
 // ip4_output: everything the kernels need of the mbuf and its metadata, read here on the lcore
 // (k_mq_tx_resolve's comment has the words).  Zero-copy: the mbuf header and the headroom the
@@ -10152,6 +10327,37 @@ static void mq_wb_tcp(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
                                            (struct cndp_tcp_seg *)&rec[2u * i + 1u]);
         edw[i] = (uint16_t)out;
         q->n_stat[out >> 16]++;
+    }
+}
+
+// tcp_segment: mq_wb_tcp over 64-byte records; then the mbuf is judged (tcb_mq_judged,
+// tcb_internal.h: the text the host twin runs) or its opt and verdict are cleared -- the device
+// decided from what submit knew -- and a judged mbuf counts under its verdict value
+static void mq_wb_tseg(cndp_gpu_mq_t *q, MqSlot *sl, uint32_t i0, uint32_t i1)
+{
+    u32x4 *rec = (u32x4 *)(sl->h + q->h_rec);
+    uint16_t *edw = (uint16_t *)(sl->h + q->h_edge);
+    for (uint32_t i = i0; i < i1; i++) {
+        if (i + MQ_PF < i1)
+            __builtin_prefetch(sl->mb[i + MQ_PF], 1);
+        const uint32_t e = edw[i];
+        if (e == MQ_EDGE_NONE) // zero-copy: outside every registered region, untouched
+            continue;
+        uint8_t *m = (uint8_t *)sl->mb[i];
+        const u32x4 r = rec[4u * i];
+        const uint32_t idx = r.x & 0xFFFFu;
+        uint64_t user = 0;
+        if (idx < q->pcb->max) // a value set while the batch was in flight may or may not show
+            user = __atomic_load_n(&q->pcb->user[idx], __ATOMIC_RELAXED);
+        struct cndp_tcp_seg *seg = (struct cndp_tcp_seg *)&rec[4u * i + 1u];
+        const uint32_t out = pcb_tcp_apply(m, mq_md_host(q, m), e, user, r.y, r.z, r.w, r.x >> 16, seg);
+        edw[i] = (uint16_t)out;
+        q->n_stat[out >> 16]++;
+        const uint32_t v = rec[4u * i + 3u].x & CNDP_TCPSEG_VERDICT;
+        if (!tcb_mq_judged(out & 0xffffu, seg))
+            rec[4u * i + 2u] = rec[4u * i + 3u] = u32x4{0u, 0u, 0u, 0u};
+        else if (v)
+            q->n_stat[CNDP_MQ_STAT_TSEG_RESET + v - 1u]++;
     }
 }
 
@@ -10448,7 +10654,16 @@ static const MqMode mq_modes[] = {
      .stage_of = mq_stage_tx, .len = true, .rec = 16, .rec_zc = true, .dev_of = mq_dev_tx,
      .stat_lo = CNDP_MQ_STAT_TX_SENT, .stat_hi = CNDP_MQ_STAT_TX_CKSUM,
      .fill = mq_fill_tx, .launch = mq_launch_tx, .wb_zc = mq_wb_tx, .wb_staged = mq_wb_tx, .count = mq_count_tx},
+    // the TCP mode's words and three bits of the lcore's (mq_fill_tseg); the record is the TCP mode's with opt
+    // and the verdict behind it; the device block holds first[] and what the first launch keeps for the second
+    {.mode = CNDP_MQ_TCP_SEGMENT, .by = MQ_BY_TSEG,
+     .stage_of = mq_stage_udp, .len = true, .rec = 64, .rec_zc = true, .seg = 16, .opt = 32,
+     .dev_of = mq_dev_tseg, .pin_of = mq_pin_tseg,
+     .stat_lo = CNDP_MQ_STAT_TCP_SEGMENT, .stat_hi = CNDP_MQ_STAT_TCP_IPOPT,
+     .stat2_lo = CNDP_MQ_STAT_TSEG_RESET, .stat2_hi = CNDP_MQ_STAT_TSEG_PRED_NONE,
+     .fill = mq_fill_tseg, .launch = mq_launch_tseg, .wb_zc = mq_wb_tseg, .wb_staged = mq_wb_tseg},
 };
+static_assert(CNDP_MQ_TCP_SEGMENT == 11u, "mq_modes[] is indexed by mode");
 
 static const MqMode *mq_mode(uint32_t mode, uint32_t by)
 {
@@ -10456,8 +10671,9 @@ static const MqMode *mq_mode(uint32_t mode, uint32_t by)
     return mode < n && mq_modes[mode].mode == mode && mq_modes[mode].by == by ? &mq_modes[mode] : nullptr;
 }
 
-// segs: cndp_gpu_mq_poll_tcp's records (nullptr: none wanted)
-static int mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, struct cndp_tcp_seg *segs, uint32_t max)
+// segs: cndp_gpu_mq_poll_tcp's records; opts, verdicts: cndp_gpu_mq_poll_tcpseg's (nullptr: not wanted)
+static int mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, struct cndp_tcp_seg *segs,
+                   struct cndp_tcp_opt *opts, uint8_t *verdicts, uint32_t max)
 {
     if (!q || (max && (!mbufs || !edges)))
         return -EINVAL;
@@ -10515,6 +10731,18 @@ static int mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, struct cndp_
                 else
                     memset(&segs[got + i], 0, sizeof(*segs));
             }
+        if (opts || verdicts) // as the writeback left them: zero unless the mbuf was judged (a failed slot: zero)
+            for (uint32_t i = 0; i < take; i++) {
+                const uint8_t *o = sl->h + q->h_rec + (uint64_t)(sl->polled + i) * q->mode->rec + q->mode->opt;
+                if (opts) {
+                    if (sl->failed)
+                        memset(&opts[got + i], 0, sizeof(*opts));
+                    else
+                        memcpy(&opts[got + i], o, sizeof(*opts));
+                }
+                if (verdicts)
+                    verdicts[got + i] = sl->failed ? (uint8_t)CNDP_TCPSEG_NONE : o[sizeof(*opts)];
+            }
         if (q->mode->count) // the mode's counters, from the edges handed back
             q->mode->count(q, edges + got, take);
         sl->polled += take;
@@ -10530,7 +10758,7 @@ static int mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, struct cndp_
 
 extern "C" int cndp_gpu_mq_poll(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, uint32_t max)
 {
-    return mq_poll(q, mbufs, edges, nullptr, max);
+    return mq_poll(q, mbufs, edges, nullptr, nullptr, nullptr, max);
 }
 
 // cndp_mqtcp.h: poll, and each returned mbuf's struct cndp_tcp_seg
@@ -10539,7 +10767,25 @@ extern "C" int cndp_gpu_mq_poll_tcp(cndp_gpu_mq_t *q, void **mbufs, uint16_t *ed
 {
     if (!q || !q->mode->seg)
         return -EINVAL;
-    return mq_poll(q, mbufs, edges, segs, max);
+    return mq_poll(q, mbufs, edges, segs, nullptr, nullptr, max);
+}
+
+// cndp_mqtcb.h: poll_tcp, and each returned mbuf's struct cndp_tcp_opt and verdict
+static_assert(sizeof(struct cndp_tcp_opt) == 16 && sizeof(struct cndp_tcp_seg) == 16, "the record's quarters");
+extern "C" int cndp_gpu_mq_poll_tcpseg(cndp_gpu_mq_t *q, void **mbufs, uint16_t *edges, struct cndp_tcp_seg *segs,
+                                       struct cndp_tcp_opt *opts, uint8_t *verdicts, uint32_t max)
+{
+    if (!q || !q->mode->opt)
+        return -EINVAL;
+    return mq_poll(q, mbufs, edges, segs, opts, verdicts, max);
+}
+
+extern "C" int cndp_gpu_mq_tcp_now(cndp_gpu_mq_t *q, uint32_t now)
+{
+    if (!q || !q->mode->opt)
+        return -EINVAL;
+    q->tcp_now = now;
+    return 0;
 }
 
 // Batches, mbufs and the cndpfwd and ip4_forward families answer on every mode (0 where the mode
@@ -10547,13 +10793,15 @@ extern "C" int cndp_gpu_mq_poll_tcp(cndp_gpu_mq_t *q, void **mbufs, uint16_t *ed
 // them: on every other mode they stay the unknown keys they were before that mode existed.
 static_assert(CNDP_MQ_STAT_BATCHES == 1 && CNDP_MQ_STAT_FWD_ARP_REQUEST == 10 && CNDP_MQ_STAT_L4_RECV == 11 &&
                   CNDP_MQ_STAT_L4_NOMD == 16 && CNDP_MQ_STAT_TCP_SEGMENT == 17 && CNDP_MQ_STAT_TCP_IPOPT == 24 &&
-                  CNDP_MQ_STAT_TX_SENT == 25 && CNDP_MQ_STAT_TX_CKSUM == 31,
+                  CNDP_MQ_STAT_TX_SENT == 25 && CNDP_MQ_STAT_TX_CKSUM == 31 && CNDP_MQ_STAT_TSEG_RESET == 32 &&
+                  CNDP_MQ_STAT_TSEG_PRED_NONE == 38 && CNDP_TCPSEG_PRED_NONE == 7,
               "cndp_gpu_mq_stat's key ranges");
 extern "C" int64_t cndp_gpu_mq_stat(const cndp_gpu_mq_t *q, int key)
 {
-    if (!q || key < CNDP_MQ_STAT_BATCHES || key > CNDP_MQ_STAT_TX_CKSUM)
+    if (!q || key < CNDP_MQ_STAT_BATCHES || key > CNDP_MQ_STAT_TSEG_PRED_NONE)
         return -EINVAL;
-    if (key <= CNDP_MQ_STAT_FWD_ARP_REQUEST || (key >= q->mode->stat_lo && key <= q->mode->stat_hi))
+    if (key <= CNDP_MQ_STAT_FWD_ARP_REQUEST || (key >= q->mode->stat_lo && key <= q->mode->stat_hi) ||
+        (key >= q->mode->stat2_lo && key <= q->mode->stat2_hi))
         return (int64_t)q->n_stat[key];
     return -EINVAL;
 }

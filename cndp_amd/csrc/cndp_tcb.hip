@@ -24,6 +24,12 @@
 //                        add per block and counter.
 // Every frame read is bounded by slab_len; no load leaves the slab.
 //
+// The image's device mirror is one buffer guarded by an event.  Every reader --
+// cndp_gpu_tcp_segment here, the mbuf queue's CNDP_MQ_TCP_SEGMENT kernels in
+// cndp_gpu.hip -- brackets its launches with tcb_dev_begin / tcb_dev_end
+// (tcb_internal.h).  The queue hands tcb_dev_begin a pinned snapshot buffer, so
+// a TCB changed between two batches costs its launch a copy and no wait.
+//
 // The byte readers are those of cndp_tcp.hip (and cndp_l4.hip), kept as a copy so
 // those translation units stay as they are.
 #include <hip/hip_runtime.h>
@@ -32,6 +38,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "tcb_internal.h"
 
@@ -238,21 +245,30 @@ static int tcb_dev_get(struct cndp_tcb_tbl *t, int dev, TcbDev **out)
     return 0;
 }
 
-static int tcb_mirror(TcbDev *d, struct cndp_tcb_tbl *t, hipStream_t s)
+// staging: NULL, or the pinned snapshot buffer of tcb_dev_begin (tcb_internal.h)
+static int tcb_mirror(TcbDev *d, struct cndp_tcb_tbl *t, hipStream_t s, void *staging)
 {
     (void)tcb_reconcile(t);
     if (d->gen == t->gen)
         return 0;
     uint32_t lo = t->d_lo, hi = t->d_hi;
+    bool wait = staging == NULL;
     if (!d->img) {
         HIP_TRY(hipMalloc((void **)&d->img, (size_t)t->cap * TCB_WORDS * 4u));
         lo = 0;
         hi = t->cap;
+        wait = true; // the first copy of a table comes from the host image itself
     }
     if (hi > lo) {
-        HIP_TRY(hipMemcpyAsync(d->img + (size_t)lo * TCB_WORDS, t->img + (size_t)lo * TCB_WORDS,
-                               (size_t)(hi - lo) * TCB_WORDS * 4u, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s)); // the host table may change after we return
+        const size_t at = (size_t)lo * TCB_WORDS, bytes = (size_t)(hi - lo) * TCB_WORDS * 4u;
+        const uint32_t *src = t->img + at;
+        if (!wait) { // the entries as they are now, where later changes do not reach them
+            memcpy((uint32_t *)staging + at, src, bytes);
+            src = (const uint32_t *)staging + at;
+        }
+        HIP_TRY(hipMemcpyAsync(d->img + at, src, bytes, hipMemcpyHostToDevice, s));
+        if (wait)
+            HIP_TRY(hipStreamSynchronize(s)); // the host table may change after we return
     }
     t->d_lo = UINT32_MAX;
     t->d_hi = 0;
@@ -260,14 +276,67 @@ static int tcb_mirror(TcbDev *d, struct cndp_tcb_tbl *t, hipStream_t s)
     return 0;
 }
 
+// tcb_dev_begin under t->lock: the device, the wait for a reader on another
+// stream, the mirror brought up to date
+static int tcb_begin_locked(struct cndp_tcb_tbl *t, int dev, hipStream_t s, void *staging, TcbDev **out)
+{
+    HIP_TRY(hipSetDevice(dev));
+    TcbDev *d = NULL;
+    int r = tcb_dev_get(t, dev, &d);
+    if (r)
+        return r;
+    if (d->have_last && d->last != s)
+        HIP_TRY(hipStreamWaitEvent(s, d->ev, 0));
+    if ((r = tcb_mirror(d, t, s, staging)))
+        return r;
+    *out = d;
+    return 0;
+}
+
+// tcb_dev_end under t->lock: the reader's end recorded
+static int tcb_end_locked(struct cndp_tcb_tbl *t, hipStream_t s, int launched)
+{
+    TcbDev *d = (TcbDev *)t->dev;
+    if (!launched || !d)
+        return 0;
+    HIP_TRY(hipEventRecord(d->ev, s));
+    d->last = s;
+    d->have_last = 1;
+    return 0;
+}
+
+extern "C" int tcb_dev_begin(struct cndp_tcb_tbl *t, int dev, void *stream, void *staging, const uint32_t **img)
+{
+    pthread_mutex_lock(&t->lock);
+    TcbDev *d = NULL;
+    const int r = tcb_begin_locked(t, dev, (hipStream_t)stream, staging, &d);
+    if (r) {
+        pthread_mutex_unlock(&t->lock);
+        return r;
+    }
+    *img = d->img;
+    return 0;
+}
+
+extern "C" int tcb_dev_end(struct cndp_tcb_tbl *t, void *stream, int launched)
+{
+    const int r = tcb_end_locked(t, (hipStream_t)stream, launched);
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
+extern "C" int tcb_dev_check(struct cndp_tcb_tbl *t, int dev)
+{
+    pthread_mutex_lock(&t->lock);
+    const TcbDev *d = (const TcbDev *)t->dev;
+    const int r = d && d->dev != dev ? -EINVAL : 0; // one table, one device
+    pthread_mutex_unlock(&t->lock);
+    return r;
+}
+
 static int tcb_run(TcbDev *d, struct cndp_tcb_tbl *t, const struct cndp_batch *b, const struct cndp_tcpseg_io *io,
                    uint32_t now, hipStream_t s)
 {
-    if (d->have_last && d->last != s)
-        HIP_TRY(hipStreamWaitEvent(s, d->ev, 0));
-    int r = tcb_mirror(d, t, s);
-    if (r || b->n == 0)
-        return r;
     SegArgs a;
     a.slab = (const uint8_t *)b->slab;
     a.slab_len = b->slab_len;
@@ -296,9 +365,6 @@ static int tcb_run(TcbDev *d, struct cndp_tcb_tbl *t, const struct cndp_batch *b
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(tcpseg_kernel, dim3(grid), dim3(SEG_BLOCK), 0, s, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev, s));
-    d->last = s;
-    d->have_last = 1;
     return 0;
 }
 
@@ -312,12 +378,15 @@ extern "C" int cndp_gpu_tcp_segment(cndp_gpu_ctx_t *ctx, cndp_tcb_tbl_t *t, cons
                  (b->slab_len >> 63)))
         return -EINVAL;
     const int dev = cndp_gpu_device(ctx);
-    HIP_TRY(hipSetDevice(dev));
     pthread_mutex_lock(&t->lock);
     TcbDev *d = NULL;
-    int r = tcb_dev_get(t, dev, &d);
-    if (!r)
-        r = tcb_run(d, t, b, io, now, (hipStream_t)stream);
+    int r = tcb_begin_locked(t, dev, (hipStream_t)stream, NULL, &d);
+    if (!r) {
+        if (b->n)
+            r = tcb_run(d, t, b, io, now, (hipStream_t)stream);
+        const int e = tcb_end_locked(t, (hipStream_t)stream, b->n && !r);
+        r = r ? r : e;
+    }
     pthread_mutex_unlock(&t->lock);
     return r;
 }

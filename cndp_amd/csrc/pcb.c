@@ -451,18 +451,22 @@ static inline uint32_t tcp_raw_sum(const uint8_t *p, uint32_t len)
     return S;
 }
 
-int cndp_tcp_input_node_host(cndp_pcb_tbl_t *t, void *const *mbufs, uint32_t n, uint16_t *edges,
-                             struct cndp_tcp_seg *segs, const void *readable_end, uint32_t stage_max,
-                             void *(*metadata)(const void *m))
+/* cndp_tcp_input_node_host's walk with t->lock held.  hits (with optw) non-NULL:
+ * also each mbuf's matched PCB index (CNDP_PCB_NONE: none, or the mbuf was not
+ * taken) and, for a header offset above 20, the PCB_TCP_OPT_WORDS little-endian
+ * words at mtod + l3_len + 20 of the mbuf as submitted, bytes past the readable
+ * ones as zero -- what cndp_tcp_segment_node_host (tcb.c) goes on from.  Inlined
+ * into its two callers with hits a constant, so that cndp_tcp_input_node_host's
+ * loop carries nothing of the other's. */
+static inline __attribute__((always_inline)) int tcp_node_walk(struct cndp_pcb_tbl *t, void *const *mbufs, uint32_t n,
+                                                               uint16_t *edges, struct cndp_tcp_seg *segs,
+                                                               uint32_t *const hits, uint32_t *const optw,
+                                                               const void *readable_end, uint32_t stage_max,
+                                                               void *(*metadata)(const void *m))
 {
-    if (!t || n > 256u || (n && (!mbufs || !edges)))
-        return -EINVAL;
-    pthread_mutex_lock(&t->lock);
-    int r = pcb_tcp_image(t);
-    if (r) {
-        pthread_mutex_unlock(&t->lock);
+    const int r = pcb_tcp_image(t);
+    if (r)
         return r;
-    }
     const uint32_t *img = t->timg;
     const uint32_t flags = img[2];
     const uintptr_t end = (uintptr_t)readable_end;
@@ -471,6 +475,8 @@ int cndp_tcp_input_node_host(cndp_pcb_tbl_t *t, void *const *mbufs, uint32_t n, 
         edges[i] = (uint16_t)CNDP_MQ_EDGE_NONE;
         if (segs)
             memset(&segs[i], 0, sizeof(segs[i]));
+        if (hits)
+            hits[i] = CNDP_PCB_NONE;
         if (!m || (end && (uintptr_t)m + 64u > end))
             continue;
         uint64_t buf, txo;
@@ -521,7 +527,35 @@ int cndp_tcp_input_node_host(cndp_pcb_tbl_t *t, void *const *mbufs, uint32_t n, 
         edges[i] = (uint16_t)out;
         if (segs)
             segs[i] = seg;
+        if (hits) { /* the option words as submitted, for a record that stands */
+            hits[i] = hit;
+            uint32_t *w = optw + (size_t)i * PCB_TCP_OPT_WORDS;
+            memset(w, 0, PCB_TCP_OPT_WORDS * sizeof(uint32_t));
+            if (seg.offset > 20u) {
+                const uint32_t nw = seg.offset <= 32u ? 4u : PCB_TCP_OPT_WORDS; /* as the kernel reads them */
+                for (uint32_t k = 0; k < nw; k++)
+                    w[k] = fr32(f, R, l3 + 20u + 4u * k);
+            }
+        }
     }
-    pthread_mutex_unlock(&t->lock);
     return 0;
+}
+
+int pcb_tcp_node_walk(struct cndp_pcb_tbl *t, void *const *mbufs, uint32_t n, uint16_t *edges,
+                      struct cndp_tcp_seg *segs, uint32_t *hits, uint32_t *optw, const void *readable_end,
+                      uint32_t stage_max, void *(*metadata)(const void *m))
+{
+    return tcp_node_walk(t, mbufs, n, edges, segs, hits, optw, readable_end, stage_max, metadata);
+}
+
+int cndp_tcp_input_node_host(cndp_pcb_tbl_t *t, void *const *mbufs, uint32_t n, uint16_t *edges,
+                             struct cndp_tcp_seg *segs, const void *readable_end, uint32_t stage_max,
+                             void *(*metadata)(const void *m))
+{
+    if (!t || n > 256u || (n && (!mbufs || !edges)))
+        return -EINVAL;
+    pthread_mutex_lock(&t->lock);
+    const int r = tcp_node_walk(t, mbufs, n, edges, segs, NULL, NULL, readable_end, stage_max, metadata);
+    pthread_mutex_unlock(&t->lock);
+    return r;
 }

@@ -352,6 +352,13 @@ int pcb_tdev_begin(struct cndp_pcb_tbl *tbl, int dev, void *stream, const uint32
 int pcb_tdev_end(struct cndp_pcb_tbl *tbl, void *stream, int launched);
 int pcb_tdev_check(struct cndp_pcb_tbl *tbl, int dev);
 
+/* cndp_tcp_input_node_host's per-mbuf walk (pcb.c), for the twins of both TCP
+ * queue modes; call with tbl->lock held.  optw: n * PCB_TCP_OPT_WORDS words. */
+#define PCB_TCP_OPT_WORDS 11u /* TCB_OPT_WORDS (tcb_internal.h) */
+int pcb_tcp_node_walk(struct cndp_pcb_tbl *tbl, void *const *mbufs, uint32_t n, uint16_t *edges,
+                      struct cndp_tcp_seg *segs, uint32_t *hits, uint32_t *optw, const void *readable_end,
+                      uint32_t stage_max, void *(*metadata)(const void *m));
+
 /* ---- tcp_input per frame (cndp_mqtcp.h): the text the queue's kernel
  * k_mq_tcp_input and the host twin cndp_tcp_input_node_host both compile */
 

@@ -2,18 +2,21 @@
  * tcb.c -- the TCB table of include/cndp_tcb.h: a per-PCB snapshot of what
  * cnet_tcp_input reads of a connection between "Segment Arrives" and the end of
  * the header-prediction tests (lib/cnet/tcp/cnet_tcp.c:3425-3482, :3214-3281),
- * kept as the image the device stage mirrors, and the stage's rule on the host
- * (cndp_tcp_segment_host).  Plain C, no HIP: it also builds into a stand-alone
+ * kept as the image the device stage mirrors, the stage's rule on the host
+ * (cndp_tcp_segment_host), and the mbuf queue's CNDP_MQ_TCP_SEGMENT mode on the
+ * host (cndp_tcp_segment_node_host, include/cndp_mqtcb.h).  Plain C, no HIP: it also builds into a stand-alone
  * program (tests/tcb_host).
  */
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/cndp_mqtcb.h"
 #include "../../include/cndp_tcpout.h"
 #include "tcb_internal.h"
 
 #define EDGE_SEG CNDP_L4_EDGE(CNDP_L4_NODE_TCP_INPUT, CNDP_TCP_INPUT_SEGMENT)
+_Static_assert(PCB_TCP_OPT_WORDS == TCB_OPT_WORDS, "pcb.c's walk hands over the option words tcb_segment() reads");
 
 int cndp_tcb_tbl_create(cndp_pcb_tbl_t *pcb_tbl, cndp_tcb_tbl_t **out)
 {
@@ -24,7 +27,9 @@ int cndp_tcb_tbl_create(cndp_pcb_tbl_t *pcb_tbl, cndp_tcb_tbl_t **out)
         return -ENOMEM;
     t->cap = pcb_tbl->max;
     t->img = calloc((size_t)t->cap * TCB_WORDS, sizeof(uint32_t));
-    if (!t->img || pthread_mutex_init(&t->lock, NULL)) {
+    t->seen = calloc(t->cap, sizeof(uint32_t));
+    if (!t->img || !t->seen || pthread_mutex_init(&t->lock, NULL)) {
+        free(t->seen);
         free(t->img);
         free(t);
         return -ENOMEM;
@@ -45,6 +50,7 @@ void cndp_tcb_tbl_destroy(cndp_tcb_tbl_t *t)
         t->dev_release(t->dev);
     free(t->kimg);
     pthread_mutex_destroy(&t->lock);
+    free(t->seen);
     free(t->img);
     free(t);
 }
@@ -278,4 +284,55 @@ int cndp_tcp_segment_host(cndp_tcb_tbl_t *t, uint32_t now, const struct cndp_bat
     free(seen);
     pthread_mutex_unlock(&t->lock);
     return 0;
+}
+
+/* ---- cndp_mqtcb.h: tcp_input, cnet_tcp_input's opening, tcp_do_options and the
+ * prediction tests over mbufs on the host ------------------------------------- */
+
+int cndp_tcp_segment_node_host(cndp_pcb_tbl_t *tbl, cndp_tcb_tbl_t *t, uint32_t now, void *const *mbufs, uint32_t n,
+                               uint16_t *edges, struct cndp_tcp_seg *segs, struct cndp_tcp_opt *opts,
+                               uint8_t *verdicts, const void *readable_end, uint32_t stage_max,
+                               void *(*metadata)(const void *m))
+{
+    if (!tbl || !t || t->pcb != tbl || n > 256u || (n && (!mbufs || !edges)))
+        return -EINVAL;
+    struct cndp_tcp_seg sg[256];
+    uint32_t hits[256], optw[256u * PCB_TCP_OPT_WORDS];
+    pthread_mutex_lock(&t->lock);
+    (void)tcb_reconcile(t);
+    pthread_mutex_lock(&tbl->lock);
+    const int r = pcb_tcp_node_walk(tbl, mbufs, n, edges, sg, hits, optw, readable_end, stage_max, metadata);
+    pthread_mutex_unlock(&tbl->lock);
+    /* FIRST: the judged mbufs are walked in batch order, and a PCB's stamp says whether this call
+     * has met it; stamps of earlier calls never equal this one's, so nothing is cleared per call */
+    if (++t->seen_call == 0u) {
+        memset(t->seen, 0, (size_t)t->cap * sizeof(uint32_t));
+        t->seen_call = 1u;
+    }
+    const uint32_t call = t->seen_call;
+    for (uint32_t i = 0; !r && i < n; i++) {
+        uint32_t o[4] = {0, 0, 0, 0}, v = CNDP_TCPSEG_NONE;
+        const uint32_t p = hits[i];
+        if (tcb_mq_judged(edges[i], &sg[i]) && p < t->cap) {
+            v = tcb_segment(t->img + (size_t)p * TCB_WORDS, sg[i].seq, sg[i].ack, sg[i].wnd, sg[i].len, sg[i].flags,
+                            sg[i].offset, optw + (size_t)i * PCB_TCP_OPT_WORDS, now, o);
+            if (t->seen[p] != call) {
+                t->seen[p] = call;
+                v |= CNDP_TCPSEG_FIRST;
+            }
+        }
+        if (segs)
+            segs[i] = sg[i];
+        if (opts) {
+            opts[i].ts_val = o[0];
+            opts[i].ts_ecr = o[1];
+            opts[i].wnd = o[2];
+            opts[i].mss = (uint16_t)o[3];
+            opts[i].sflags = (uint16_t)(o[3] >> 16);
+        }
+        if (verdicts)
+            verdicts[i] = (uint8_t)v;
+    }
+    pthread_mutex_unlock(&t->lock);
+    return r;
 }

@@ -39,11 +39,33 @@ struct cndp_tcb_tbl {
     /* transmit side (include/cndp_tcpout.h) */
     uint32_t *kimg;       /* PCB key image (tcpout_internal.h), allocated on first use */
     uint64_t kimg_gen;    /* pcb->gen the key image was built from (0 = never) */
+    /* the queue mode's host twin (include/cndp_mqtcb.h) */
+    uint32_t *seen;       /* cap stamps: the twin call that last judged a segment of the PCB */
+    uint32_t seen_call;   /* the current call's stamp, never 0 */
 };
 
 /* Call with t->lock held: take the TCBs of PCBs deleted since the last look
  * away, and return the PCB vector's length. */
 uint32_t tcb_reconcile(struct cndp_tcb_tbl *t);
+
+/* Readers of the image's device mirror (cndp_tcb.hip): cndp_gpu_tcp_segment and
+ * the mbuf queue's CNDP_MQ_TCP_SEGMENT kernels in cndp_gpu.hip.  The protocol is
+ * pcb_tdev_begin / _end / _check's (pcb_internal.h).  tcb_dev_begin takes
+ * t->lock, orders `stream` after a reader on another stream, brings the mirror
+ * up to date on `stream` and answers the mirror's address; the lock is held
+ * until tcb_dev_end, which records the reader's end where it launched.  A
+ * reader that takes both tables begins this one first and ends it last: t->lock
+ * is taken before pcb->lock.
+ * staging = NULL: changed entries are copied from the host image and the copy is
+ * waited for, as the host image may change once the lock is gone.  staging =
+ * pinned memory of t->cap * TCB_WORDS * 4 bytes that the caller leaves alone until
+ * the work it enqueues next on `stream` has completed: the changed entries are
+ * snapshot there and copied from there, and nothing is waited for -- stream order
+ * keeps the copy behind the stream's earlier readers.  The mirror's allocation,
+ * at a table's first use, waits either way. */
+int tcb_dev_begin(struct cndp_tcb_tbl *t, int dev, void *stream, void *staging, const uint32_t **img);
+int tcb_dev_end(struct cndp_tcb_tbl *t, void *stream, int launched);
+int tcb_dev_check(struct cndp_tcb_tbl *t, int dev);
 
 #define TCB_TCP_FIN 0x01u
 #define TCB_TCP_SYN 0x02u
@@ -155,6 +177,43 @@ static inline PCB_HD uint32_t tcb_segment(const uint32_t *e, uint32_t seq, uint3
     } else if (ack == e[1] && (e[10] & CNDP_TCB_REASS_EMPTY) && len <= e[8])
         v ^= CNDP_TCPSEG_PRED_NONE ^ CNDP_TCPSEG_PRED_DATA;
     return v;
+}
+
+/* ---- cndp_mqtcb.h: which mbufs of the queue's CNDP_MQ_TCP_SEGMENT mode are judged */
+
+/* Step 11 from the mbuf's final edge and record, as pcb_tcp_apply left them:
+ * poll (cndp_gpu.hip) and the twin (tcb.c).  A record that stands has a header
+ * offset of 20 or more; the zeroed one of an IPOPT mbuf has none. */
+static inline int tcb_mq_judged(uint32_t edge, const struct cndp_tcp_seg *seg)
+{
+    return (edge & CNDP_MQ_EDGE_TCP_MASK) == PCB_TCP_E(CNDP_TCP_INPUT_SEGMENT) && seg->offset != 0u;
+}
+
+/* What the lcore knows at submit and the device does not (pcb_tcp_apply's tests on
+ * the metadata hook and the mbuf's lengths): the mode's fill sets these in the
+ * frame word, bits 40-42. */
+#define TCB_MQ_NOMD 1u   /* step 1: metadata(m) == NULL */
+#define TCB_MQ_ADJUST 2u /* step 7: l3_len == 20 and pktmbuf_adjust fails */
+#define TCB_MQ_SHORT 4u  /* step 8: l3_len == 20 and rx_short */
+
+static inline uint32_t tcb_mq_host_bits(int nomd, uint32_t l3, uint32_t doff, uint32_t blen, uint32_t dlen)
+{
+    uint32_t b = nomd ? TCB_MQ_NOMD : 0u;
+    if (l3 == 20u) {
+        if (l3 > dlen || l3 + doff > blen)
+            b |= TCB_MQ_ADJUST;
+        else if (dlen - l3 < 20u)
+            b |= TCB_MQ_SHORT;
+    }
+    return b;
+}
+
+/* The same decision on the device, before poll has run: edge = pcb_tcp_rule's with
+ * the verify's verdict in, bits = the lcore's, offset / tot the header's.  rx_badoff
+ * drops an l3_len == 20 mbuf and zeroes the record of every other. */
+static inline PCB_HD int tcb_mq_judged_dev(uint32_t edge, uint32_t bits, uint32_t offset, uint32_t tot)
+{
+    return edge == PCB_TCP_E(CNDP_TCP_INPUT_SEGMENT) && !bits && offset >= 20u && offset <= tot;
 }
 
 #ifdef __cplusplus

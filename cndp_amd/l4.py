@@ -223,6 +223,26 @@ def seg_records(seg) -> np.ndarray:
 # ---------------------------------------------------------------------------
 # struct cndp_tcp_opt
 OPT_DT = np.dtype([("ts_val", "<u4"), ("ts_ecr", "<u4"), ("wnd", "<u4"), ("mss", "<u2"), ("sflags", "<u2")])
+
+
+def tcp_segment_node_host(tbl: "PcbTable", tcbs: "TcbTable", ptrs, n: int | None = None, now: int = 0,
+                          readable_end=None, stage_max: int = 0, metadata=None):
+    """cndp_tcp_segment_node_host (include/cndp_mqtcb.h): the mbuf queue's
+    CNDP_MQ_TCP_SEGMENT mode on the calling thread over one batch of n <= 256
+    mbufs, edited in place as tcp_input_node_host edits them.  Returns
+    (edges, segs, opts, verdicts): SEG_DT and OPT_DT record arrays, uint8."""
+    n = len(ptrs) if n is None else n
+    edges = np.zeros(max(n, 1), np.uint16)
+    segs = np.zeros(max(n, 1), SEG_DT)
+    opts = np.zeros(max(n, 1), OPT_DT)
+    verdicts = np.zeros(max(n, 1), np.uint8)
+    fn = METADATA_FN(metadata) if metadata else None
+    N.check(N.lib().cndp_tcp_segment_node_host(tbl.h, tcbs.h, now & 0xFFFFFFFF, ptrs, n, edges.ctypes.data,
+                                               segs.ctypes.data, opts.ctypes.data, verdicts.ctypes.data,
+                                               readable_end, stage_max,
+                                               ctypes.cast(fn, ctypes.c_void_p) if fn else None),
+            "cndp_tcp_segment_node_host")
+    return edges[:n], segs[:n], opts[:n], verdicts[:n]
 # struct cndp_tcp_txseg
 TXSEG_DT = np.dtype([("seq", "<u4"), ("ack", "<u4"), ("wnd", "<u2"), ("urp", "<u2"), ("len", "<u2"),
                      ("flags", "u1"), ("rsvd", "u1")])

@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 
 from . import native as N
-from .l4 import SEG_DT
+from .l4 import OPT_DT, SEG_DT
 
 # struct pktmbuf_s, 64 bytes (pktmbuf.h:102-204)
 MBUF_DT = np.dtype([("pooldata", "<u8"), ("buf_addr", "<u8"), ("hash", "<u4"), ("meta_index", "<u4"),
@@ -114,7 +114,7 @@ class MbufQueue:
     def __init__(self, cl, mode: int, flags: int = 0, batch: int = 8192, depth: int = 4,
                  max_delay_us: int = 50, umem=None, lport: int = 0, stage_max: int = 0, metadata=None,
                  fib=None, acl=None, acl_mode: int = N.CNDP_ACL_STRICT, acl_flags: int = 0, lports=(),
-                 fwd_tbl=None, pcb_tbl=None, tx_mode: int = N.CNDP_TX_UDP):
+                 fwd_tbl=None, pcb_tbl=None, tx_mode: int = N.CNDP_TX_UDP, tcb=None):
         """metadata: cnet's pktmbuf_metadata hook, a Python function of the mbuf
         address returning the metadata address (None: m + 64).
         cndpfwd modes (CNDP_MQ_CFWD_FWD / _L3FWD / CNDP_MQ_ACL_FWD, cndp_mqfwd.h):
@@ -130,9 +130,11 @@ class MbufQueue:
         looks connections up in; the create call is chosen by the mode.
         CNDP_MQ_IP4_OUTPUT (cndp_mqtx.h): fwd_tbl and pcb_tbl are the tables
         udp_output + ip4_output resolve in, tx_mode is CNDP_TX_UDP or
-        CNDP_TX_IP4; metadata is the hook submit calls."""
+        CNDP_TX_IP4; metadata is the hook submit calls.
+        CNDP_MQ_TCP_SEGMENT (cndp_mqtcb.h): pcb_tbl as for CNDP_MQ_TCP_INPUT and
+        tcb the l4.TcbTable made over it; metadata is called by submit and poll."""
         self._L = N.lib()
-        self._keep = (fib, acl, fwd_tbl, pcb_tbl)
+        self._keep = (fib, acl, fwd_tbl, pcb_tbl, tcb)
         c = N.MqConf()
         c.mode, c.flags, c.batch, c.depth = mode, flags, batch, depth
         c.max_delay_us, c.stage_max, c.lport = max_delay_us, stage_max, lport
@@ -157,6 +159,11 @@ class MbufQueue:
                                                           fwd_tbl.h if fwd_tbl is not None else None,
                                                           pcb_tbl.h if pcb_tbl is not None else None, tx_mode,
                                                           ctypes.byref(h)), "cndp_gpu_mq_create_ip4_output")
+        elif mode == N.CNDP_MQ_TCP_SEGMENT:
+            N.check(self._L.cndp_gpu_mq_create_tcp_segment(cl.h, ctypes.byref(c),
+                                                           pcb_tbl.h if pcb_tbl is not None else None,
+                                                           tcb.h if tcb is not None else None, ctypes.byref(h)),
+                    "cndp_gpu_mq_create_tcp_segment")
         elif fwd_tbl is not None:
             N.check(self._L.cndp_gpu_mq_create_ip4_forward(cl.h, ctypes.byref(c), fwd_tbl.h, ctypes.byref(h)),
                     "cndp_gpu_mq_create_ip4_forward")
@@ -215,6 +222,40 @@ class MbufQueue:
         k = N.check(self._L.cndp_gpu_mq_poll_tcp(self.h, out, edges.ctypes.data, segs.ctypes.data, max_n),
                     "cndp_gpu_mq_poll_tcp")
         return np.array([x or 0 for x in out[:k]], dtype=np.uint64), edges[:k].copy(), segs[:k].copy()
+
+    def set_now(self, now: int):
+        """cndp_gpu_mq_tcp_now (include/cndp_mqtcb.h): stk_get_timer_ticks() for
+        the batches launched from here on."""
+        N.check(self._L.cndp_gpu_mq_tcp_now(self.h, now & 0xFFFFFFFF), "cndp_gpu_mq_tcp_now")
+
+    def poll_tcpseg(self, max_n: int = 1 << 16):
+        """cndp_gpu_mq_poll_tcpseg (include/cndp_mqtcb.h): poll_tcp, and each
+        returned mbuf's struct cndp_tcp_opt (l4.OPT_DT) and verdict (uint8)."""
+        out = (ctypes.c_void_p * max_n)()
+        edges = np.zeros(max_n, np.uint16)
+        segs = np.zeros(max_n, SEG_DT)
+        opts = np.zeros(max_n, OPT_DT)
+        verdicts = np.zeros(max_n, np.uint8)
+        k = N.check(self._L.cndp_gpu_mq_poll_tcpseg(self.h, out, edges.ctypes.data, segs.ctypes.data, opts.ctypes.data,
+                                                    verdicts.ctypes.data, max_n), "cndp_gpu_mq_poll_tcpseg")
+        return (np.array([x or 0 for x in out[:k]], dtype=np.uint64), edges[:k].copy(), segs[:k].copy(),
+                opts[:k].copy(), verdicts[:k].copy())
+
+    def run_tcpseg(self, pool: MbufPool, idx, bursts):
+        """run() with poll_tcpseg: (addresses, edges, segs, opts, verdicts) in
+        completion order."""
+        segs, opts, verdicts = [], [], []
+
+        def poll():
+            a, e, s, o, v = self.poll_tcpseg()
+            segs.append(s)
+            opts.append(o)
+            verdicts.append(v)
+            return a, e
+        a, e = self.run(pool, idx, bursts, poll=poll)
+        if not segs:
+            return a, e, np.zeros(0, SEG_DT), np.zeros(0, OPT_DT), np.zeros(0, np.uint8)
+        return a, e, np.concatenate(segs), np.concatenate(opts), np.concatenate(verdicts)
 
     def run_tcp(self, pool: MbufPool, idx, bursts):
         """run() with poll_tcp: (addresses, edges, segs) in completion order."""

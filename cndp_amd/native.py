@@ -2,8 +2,8 @@
 include/cndp_node.h, include/cndp_gpu.h, include/cndp_l4.h,
 include/cndp_tcp.h, include/cndp_tcb.h, include/cndp_fwd.h, include/cndp_tx.h,
 include/cndp_acl.h, include/cndp_cfwd.h, include/cndp_mqfwd.h,
-include/cndp_mqcnet.h, include/cndp_mql4.h, include/cndp_mqtcp.h and
-include/cndp_mqtx.h).
+include/cndp_mqcnet.h, include/cndp_mql4.h, include/cndp_mqtcp.h,
+include/cndp_mqtx.h and include/cndp_mqtcb.h).
 
 The library is built in-tree (cndp_amd/lib/libcndp_gpu.so, see build.py).
 There is no fallback: if the shared object is missing, importing the
@@ -177,6 +177,10 @@ CNDP_MQ_EDGE_TX_CKSUM = 0x1000
 CNDP_MQ_TX_CAUSE_NOMD, CNDP_MQ_TX_CAUSE_HEADROOM, CNDP_MQ_TX_CAUSE_NOROUTE, CNDP_MQ_TX_CAUSE_PROTO = 1, 2, 3, 4
 (CNDP_MQ_STAT_TX_SENT, CNDP_MQ_STAT_TX_ARP_REQUEST, CNDP_MQ_STAT_TX_DROP_NOMD, CNDP_MQ_STAT_TX_DROP_HEADROOM,
  CNDP_MQ_STAT_TX_DROP_NOROUTE, CNDP_MQ_STAT_TX_DROP_PROTO, CNDP_MQ_STAT_TX_CKSUM) = range(25, 32)
+# cndp_mqtcb.h
+CNDP_MQ_TCP_SEGMENT = 11
+(CNDP_MQ_STAT_TSEG_RESET, CNDP_MQ_STAT_TSEG_CLOSED, CNDP_MQ_STAT_TSEG_BADOPT, CNDP_MQ_STAT_TSEG_SLOW,
+ CNDP_MQ_STAT_TSEG_PRED_ACK, CNDP_MQ_STAT_TSEG_PRED_DATA, CNDP_MQ_STAT_TSEG_PRED_NONE) = range(32, 39)
 
 
 def CNDP_MQ_EDGE_TX_CAUSE(e: int) -> int:
@@ -484,6 +488,12 @@ def lib():
         "cndp_gpu_mq_poll_tcp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
         "cndp_tcp_input_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32,
                                              c_void_p]),
+        # cndp_mqtcb.h
+        "cndp_gpu_mq_create_tcp_segment": (c_int, [c_void_p, POINTER(MqConf), c_void_p, c_void_p, POINTER(c_void_p)]),
+        "cndp_gpu_mq_tcp_now": (c_int, [c_void_p, c_uint32]),
+        "cndp_gpu_mq_poll_tcpseg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
+        "cndp_tcp_segment_node_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
         # cndp_mqtx.h
         "cndp_gpu_mq_create_ip4_output": (c_int, [c_void_p, POINTER(MqConf), c_void_p, c_void_p, c_uint32,
                                                   POINTER(c_void_p)]),
@@ -530,7 +540,7 @@ def exported_symbols():
     names = []
     inc = os.path.join(os.path.dirname(HERE), "include")
     for h in ("cndp_fib.h", "cndp_node.h", "cndp_gpu.h", "cndp_mqfwd.h", "cndp_mqcnet.h", "cndp_mql4.h", "cndp_mqtcp.h",
-              "cndp_mqtx.h"):
+              "cndp_mqtx.h", "cndp_mqtcb.h"):
         with open(os.path.join(inc, h)) as f:
             txt = f.read()
         names += re.findall(r"^[A-Za-z_][\w \*]*?\b((?:cne|cndp|ip4)_\w+)\s*\(", txt, re.M)

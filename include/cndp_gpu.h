@@ -227,8 +227,10 @@ typedef struct cndp_gpu_mq cndp_gpu_mq_t;
  * table: cndp_mqcnet.h (cndp_gpu_mq_create_ip4_forward); mode 8, cnet's
  * ip4_proto + udp_input nodes, needs a PCB table: cndp_mql4.h
  * (cndp_gpu_mq_create_udp_input); mode 9, cnet's tcp_input node, needs a TCP
- * PCB table: cndp_mqtcp.h (cndp_gpu_mq_create_tcp_input); cndp_gpu_mq_create
- * answers -EINVAL for them */
+ * PCB table: cndp_mqtcp.h (cndp_gpu_mq_create_tcp_input); mode 11, that node
+ * with tcp_do_options and the header-prediction tests behind it, needs the TCB
+ * table as well: cndp_mqtcb.h (cndp_gpu_mq_create_tcp_segment);
+ * cndp_gpu_mq_create answers -EINVAL for them */
 #define CNDP_MQ_F_HASH (1u << 0)
 #define CNDP_MQ_F_NO_METADATA (1u << 1) /* cnet: leave cnet_metadata unwritten */
 /* Zero-copy ip4_lookup and cnet: the host hands over mbuf pointers only and
